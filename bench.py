@@ -7,13 +7,25 @@ One step = one tlsgpu_open_batch over the whole resident batch (64 Ki records,
 1 GiB of ciphertext in HBM -> 1 GiB of plaintext in HBM + per-record status).
 Inputs are synthetic (counter-SplitMix64 plaintexts, 1024 sessions x 64 records,
 1/1024 records tampered), sealed on the device beforehand by the validated
-sealer; the first step's outputs are verified before the warm-up steps (so the
-GPU is busy up to the timed region) and the last timed step's after it.  Before
-the W warm-up steps an untimed settle (--settle-ms, default 100 ms of
-back-to-back steps) lets the GPU clock leave the dip a fresh sustained load
-causes, so the K timed steps measure the steady state.
+sealer.  Before the W warm-up steps an untimed settle (--settle-ms, default
+100 ms of back-to-back steps) lets the GPU clock leave the dip a fresh
+sustained load causes, so the K timed steps measure the steady state
+(DESIGN.md §5).
 
-  python bench.py [--gpus N] [--steps K] [--warmup W] [--config B|C|D]
+A plain run does what the headline figure needs and no more: set-up, settle,
+W warm-up steps, the K timed steps, the result line.  --full adds what else the
+benchmark checks and measures: the first step's outputs are verified before
+the warm-up steps (so the GPU is busy up to the timed region) and the last
+timed step's after it, and the CPU baseline runs (`cpu_baseline`, ~20 s of CPU
+work).  --dump-outputs DIR writes what the last timed step computed as
+DIR/<name>.npy (float32): `status` (every record's status) and `plaintext`
+(the opened bytes of a fixed, seeded sample of records, tampered ones among
+them, in record order; config C also `sealed`, the sampled records' sealed
+fragments), so two builds can be compared output for output — the inputs are
+the same on every run with the same arguments.
+
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--full] [--dump-outputs DIR]
+                  [--config B|C|D]
                   [--sessions S] [--interleave] [--mode device|host|wire|copy]
                   [--split group|ranks] [--devices 0,1,...]
   N>1: python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N
@@ -26,8 +38,9 @@ causes, so the K timed steps measure the steady state.
 
 Prints ONE JSON line (rank 0).  `roofline.achieved` = algorithmic bytes per
 launch / average launch time from HIP events on the engine stream;
-`cpu_baseline` = the reference LibreSSL EVP_AEAD_CTX_open (oracle/_ref/libref.so,
-compiled from the reference sources) on a bounded sample on this host.
+`cpu_baseline` (--full) = the reference LibreSSL EVP_AEAD_CTX_open
+(oracle/_ref/libref.so, compiled from the reference sources) on a bounded
+sample on this host.
 """
 from __future__ import annotations
 
@@ -250,7 +263,14 @@ def main():
     ap.add_argument("--interleave", action="store_true",
                     help="deal records to sessions round-robin (a many-connection server "
                          "batch) instead of grouping each session's records")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also what the headline figure does not need: verify the first and "
+                         "the last timed step's outputs, run the CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's outputs (statuses, a seeded sample of "
+                         "the opened records) as DIR/<name>.npy")
+    ap.add_argument("--no-cpu-baseline", action="store_true",
+                    help="with --full: skip the CPU baseline")
     ap.add_argument("--no-hints", action="store_true",
                     help="do not state the batch-shape hints (tlsgpu_sessions_hint) the "
                          "workload's lengths and session order imply")
@@ -270,6 +290,10 @@ def main():
                          "in-place open, SURVEY.md §8f-1); copy: the box's achievable "
                          "device-to-device copy bandwidth (hipMemcpy, 1 GiB)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if args.dump_outputs and args.mode != "device":
+        ap.error("--dump-outputs is for --mode device")
 
     import talos_amd as ta
     from talos_amd.dist import ControlPlane, device_for, env_rank, shard_by_bytes
@@ -278,6 +302,8 @@ def main():
     world, rank, local = env_rank()
     if choose_split(args.split, world, args.devices, args.gpus) == "group" and args.mode == "device":
         return group_mode(args, world, rank)
+    if args.dump_outputs and world > 1:
+        raise SystemExit("--dump-outputs writes from one process: use the group split for N > 1")
     ta.load_library()
     eng = ta.Engine(device_for(local, ta.device_count()))  # first GPU runtime user
     if args.mode == "copy":
@@ -334,13 +360,14 @@ def main():
             wl.seal(stream)
             wl.open(stream)
 
-    # the first step's outputs are verified before the warm-up, not after it:
-    # the verification's host round trips leave the GPU idle for tens of ms,
-    # and the timed region must start at the working clock the warm-up reached
-    # (profiles/r05ag_bench_warm_start.txt)
+    # --full: the first step's outputs are verified before the warm-up, not
+    # after it: the verification's host round trips leave the GPU idle for tens
+    # of ms, and the timed region must start at the working clock the warm-up
+    # reached (profiles/r05ag_bench_warm_start.txt)
     step()
     eng.sync()
-    wl.verify_open()
+    if args.full:
+        wl.verify_open()
     settled = settle(step, eng.sync, args.settle_ms)
     for _ in range(max(1, args.warmup)):
         step()
@@ -375,7 +402,10 @@ def main():
                       f"{st[2*i+1]/args.steps:9.0f} cycles/event {st[2*i]/st[2*i+1]:9.0f}",
                       file=sys.stderr)
     barrier()
-    wl.verify_open()
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, [wl], op == "seal+open")
+    if args.full:
+        wl.verify_open()
 
     elapsed_s, wall_s = cp.max([dev_ms / 1e3, wall_ms / 1e3])
     total_payload = cp.sum([float(total_len)])[0]
@@ -441,7 +471,7 @@ def main():
                                "per-record constants; else bounds + prep passes + main kernels)",
                      **comp},
     }
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if rank == 0 and world == 1 and args.full and not args.no_cpu_baseline:
         if rec_len:
             line["cpu_baseline"] = cpu_baseline(kind_name, rec_len, op)
         else:  # mixed lengths: the first 16 Ki records of the workload's own Zipf mix
@@ -453,6 +483,45 @@ def main():
     wl.free()
     cp.close()
     eng.close()
+
+
+DUMP_SEED = 0xD0C5
+DUMP_SAMPLE_BYTES = 8 << 20   # sampled output bytes over all arrays: 32 MiB as float32
+
+
+def dump_sample(wl, budget: int) -> np.ndarray:
+    """The records whose outputs a dump holds: the first tampered ones (their
+    plaintext must be zero-filled), then records in a seeded random order while
+    their plaintexts fit in `budget` bytes; sorted.  The same for every run of
+    the same workload."""
+    first = np.nonzero(wl.tampered)[0][:4]
+    order = np.random.default_rng(DUMP_SEED).permutation(wl.n)
+    order = np.concatenate([first, order[~np.isin(order, first)]])
+    keep = max(1, int(np.searchsorted(np.cumsum(wl.lengths[order]), budget, side="right")))
+    return np.sort(order[:keep])
+
+
+def dump_outputs(path: str, wls, sealed: bool) -> None:
+    """What the last step left in each workload's output buffers, as float32
+    .npy files under `path` (at most 64 MB in all): every record's status, and
+    the opened plaintext bytes (with `sealed` also the sealed fragments) of
+    dump_sample's records, concatenated in record order.  Several workloads
+    (group members): one set of files each, named ..._gpu<k>."""
+    import talos_amd as ta
+    os.makedirs(path, exist_ok=True)
+    budget = DUMP_SAMPLE_BYTES // (len(wls) * (2 if sealed else 1))
+    for k, wl in enumerate(wls):
+        sfx = f"_gpu{k}" if len(wls) > 1 else ""
+        np.save(os.path.join(path, f"status{sfx}.npy"), wl.status().astype(np.float32))
+        idx = dump_sample(wl, budget)
+        arrays = [("plaintext", wl.d_out, wl.pt_off, wl.lengths)]
+        if sealed:
+            arrays.append(("sealed", wl.d_body, wl.body_off,
+                           wl.lengths + ta.EXPLICIT_NONCE_LEN[wl.kind] + ta.TAG_LEN))
+        for name, buf, offs, lens in arrays:
+            parts = [buf.download(int(lens[i]), int(offs[i])) for i in idx if lens[i]]
+            data = np.concatenate(parts) if parts else np.zeros(0, np.uint8)
+            np.save(os.path.join(path, f"{name}{sfx}.npy"), data.astype(np.float32))
 
 
 def settle(step, sync, ms: float) -> dict:
@@ -564,10 +633,11 @@ def group_mode(args, world, rank):
             wl.lengths + ta.EXPLICIT_NONCE_LEN[kind] + ta.TAG_LEN, wl.session, seal=False)
         ta._check(g.lib.tlsgpu_sessions_hint(g.lib.tlsgpu_group_sessions_member(gs.handle, k),
                                              hints), "tlsgpu_sessions_hint")
-    gs.batch(shard_arr, seal=False)     # verified first, then warmed (as the device mode)
+    gs.batch(shard_arr, seal=False)     # --full: verified first, then warmed (as the device mode)
     g.sync()
-    for wl in wls:
-        wl.verify_open()
+    if args.full:
+        for wl in wls:
+            wl.verify_open()
     evs = [(ta.Event(m), ta.Event(m)) for m in members]
     settled = settle(lambda: gs.batch(shard_arr, seal=False), g.sync, args.settle_ms)
     for _ in range(max(1, args.warmup)):
@@ -583,8 +653,11 @@ def group_mode(args, world, rank):
     g.sync()
     wall_s = time.perf_counter() - t0
     dev_ms = [e0.elapsed_ms(e1) for e0, e1 in evs]
-    for wl in wls:
-        wl.verify_open()
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, wls, False)
+    if args.full:
+        for wl in wls:
+            wl.verify_open()
     total_len = sum(int(wl.lengths.sum()) for wl in wls)
     # the same timing method as N = 1: HIP events around the K steps on each
     # member's stream; the slowest member sets the step time (max over GPUs,
@@ -627,7 +700,7 @@ def group_mode(args, world, rank):
                                "its one stream); wall_value: wall clock around the K group "
                                "calls + tlsgpu_group_sync"},
     }
-    if n == 1 and not args.no_cpu_baseline:
+    if n == 1 and args.full and not args.no_cpu_baseline:
         line["cpu_baseline"] = cpu_baseline(kind_name, rec_len, op)
     print(json.dumps(line), flush=True)
     for e0, e1 in evs:

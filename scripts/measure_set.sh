@@ -19,12 +19,12 @@ run() {  # name, bench args...
   return $rc
 }
 run copy --mode copy --steps 20 &&
-run B &&
+run B --full &&
 run B_S1 --sessions 1 --no-cpu-baseline &&
 run B_S65536 --sessions 65536 --no-cpu-baseline &&
 run B_inter1024 --sessions 1024 --interleave --no-cpu-baseline &&
-run C --config C &&
-run D --config D &&
+run C --config C --full &&
+run D --config D --full &&
 run host_B --mode host --no-cpu-baseline --steps 8 --warmup 2 &&
 run pcie --mode pcie &&
 run wire_B --mode wire --no-cpu-baseline &&

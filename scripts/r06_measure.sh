@@ -16,7 +16,7 @@ run() {  # name, bench args...
   echo "bench $n rc=$rc $(cut -c1-220 $O/bench_$n.json)"
   return $rc
 }
-run B_driver --gpus 1 --steps 20 --warmup 5 &&
+run B_driver --gpus 1 --steps 20 --warmup 5 --full &&
 run B_driver2 --gpus 1 --steps 20 --warmup 5 --no-cpu-baseline &&
 run C_driver --config C --steps 20 --warmup 5 --no-cpu-baseline &&
 run D_driver --config D --steps 20 --warmup 5 --no-cpu-baseline &&
@@ -24,8 +24,8 @@ run B --no-cpu-baseline &&
 run B_S1 --sessions 1 --no-cpu-baseline &&
 run B_S65536 --sessions 65536 --no-cpu-baseline &&
 run B_inter1024 --sessions 1024 --interleave --no-cpu-baseline &&
-run C --config C &&
-run D --config D &&
+run C --config C --full &&
+run D --config D --full &&
 run copy --mode copy --steps 20 &&
 run host_B --mode host --no-cpu-baseline --steps 8 --warmup 2 &&
 run pcie --mode pcie &&

