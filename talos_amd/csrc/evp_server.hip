@@ -27,7 +27,7 @@
 // Termination: every workgroup exits when the stop word is set or after
 // `lifetime` ticks of the 100 MHz realtime counter (checked before every poll,
 // so a busy workgroup leaves on time too), whichever is first; the
-// host relaunches (engine.cpp EvpServer) so that a job is only ever posted
+// host relaunches (evp_doorbell.cpp EvpServer) so that a job is only ever posted
 // while an instance that will poll for at least half a lifetime is queued.
 #define TG_VECTOR_SESSION_LOADS 1
 // job phase marks (TLSGPU_EVP_DOORBELL_TRACE): thread t (0: wave 0, lane 0)
@@ -57,7 +57,7 @@ __device__ __forceinline__ bool tg_stage_ok(const RawJob* J) {
   return n != 0 && n <= kSrvStageMax && (J->in & 15) == 0;
 }
 // waves 12..15: 256 lanes x 16 B; the staging buffer rounds the input up to
-// 16 B (engine.cpp gpu_call_impl), so a whole 16 B read stays inside it
+// 16 B (evp_aead.cpp stage_job), so a whole 16 B read stays inside it
 __device__ __forceinline__ void tg_stage_issue(const RawJob* J, uint32_t wave, uint32_t lane) {
   if (wave < kSrvStageWave) return;
   const uint32_t off = 16 * ((wave - kSrvStageWave) * kWave + lane);
@@ -75,7 +75,7 @@ namespace tg {
 constexpr uint32_t kSrvExit = 0xFFFFFFFFu;
 constexpr uint32_t kSrvFlush = 0xFFFFFFFEu;  // zero this workgroup's key copies (a scrub elsewhere)
 // DoorbellSlot::op beyond bit 0 (seal), bits 8-15 (10 / 14 AES rounds, 20
-// ChaCha) and bit 16 (inline nonce / AAD) — engine.cpp writes the same bits
+// ChaCha) and bit 16 (inline nonce / AAD) — evp_aead.cpp post_job writes the same bits
 constexpr uint32_t kOpInstall = kDoorbellOpInstall;            // the image at inl[0..7] first
 constexpr uint32_t kOpInstallTables = kDoorbellOpInstallTables;  // ... with its GCM tables
 constexpr uint32_t kOpScrub = kDoorbellOpScrub;                  // zero the slot (bits 8-15)
@@ -85,11 +85,11 @@ constexpr uint32_t SRV_SLOT_OFF = PLAN_OFF + 512;     // LDS copy of the picked 
 static_assert(PLAN_OFF + 288 <= SRV_SLOT_OFF, "server LDS plan");
 static_assert(SRV_SLOT_OFF + sizeof(DoorbellSlot) <= SRV_STAGE_OFF, "server LDS plan");
 static_assert(SRV_STAGE_OFF + 4096 <= SRV_MARK_OFF, "server LDS plan");
-static_assert(SRV_MARK_OFF + 88 <= SRV_MARK_OFF + 128, "11 job marks before the session copy");
 // the GCM job's DevSession, copied into LDS once per installed key: the job's
 // session reads (kind, rounds, tag_len, round keys) are then LDS reads, not
 // one dependent HBM round trip each (round-4 trace: parse + setup ≈ 2.3 µs)
 constexpr uint32_t SRV_SESS_OFF = SRV_MARK_OFF + 128;
+static_assert(SRV_MARK_OFF + 8 * 11 <= SRV_SESS_OFF, "11 job marks before the session copy");
 static_assert(SRV_SESS_OFF % 16 == 0 && SRV_SESS_OFF + sizeof(DevSession) <= LDS_BYTES,
               "server LDS plan");
 // slot words the copy needs (DoorbellSlot layout, tlsgpu_internal.h)
@@ -335,7 +335,7 @@ __global__ __launch_bounds__(kThreads, 1) void evp_server_kernel(ServerArgs s) {
     if (((op >> 8) == 10 || (op >> 8) == 14) && tg_stage_ok(&c->job))
       tg_stage_issue(&c->job, wave, threadIdx.x & 63);
     if (c->op & kOpInstall) {
-      // EVP_AEAD_CTX_init's deferred install (round 5, engine.cpp): the image
+      // EVP_AEAD_CTX_init's deferred install (round 5, evp_aead.cpp): the image
       // the host built (session_host.cpp) goes from pinned memory into the
       // slot in HBM, and the DevSession also into the LDS copy, before the job
       // reads either; the GCM tables only when bit 18 says the image has them

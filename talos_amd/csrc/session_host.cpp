@@ -35,7 +35,7 @@ namespace {
 // intrinsics only: no load, store or branch here is indexed by key material
 // (no S-box table, no 4-bit GHASH table walk).  A host without AES-NI or
 // PCLMUL gets no host image at all: host_crypto_ok() is false, and the engine
-// installs through the device kernel instead (engine.cpp g_device_install).
+// installs through the device kernel instead (evp_aead.cpp g_device_install).
 
 struct U128 {
   uint64_t hi, lo;  // big-endian halves: x^0 is the MSB of hi (gcm128.c)
@@ -144,7 +144,7 @@ __attribute__((target("aes,sse4.1"))) void aes_zero_block_aesni(const __m128i (&
   _mm_storeu_si128(reinterpret_cast<__m128i*>(out), x);
 }
 
-// a function-local static: engine.cpp's static initialisers ask before this
+// a function-local static: evp_aead.cpp's static initialisers ask before this
 // translation unit's globals are guaranteed to be initialised
 bool cpu_has_aesni_pclmul() {
   static const bool ok = [] {
@@ -256,7 +256,7 @@ bool host_session_image(const tlsgpu_session_params& p, DevSession* s, DevGcmTab
 
 // The Shoup entries of a compact image (host_session_image(..., compact)):
 // each power's 16 entries from its m[8] = H^e, for a path that uploads the
-// whole image (the launched first call, engine.cpp gpu_call_impl).
+// whole image (the launched first call, evp_aead.cpp launch_job).
 void host_image_complete(DevGcmTables* t) {
   U128 m[16];
   for (int e = 1; e <= kPowMax; e++) {

@@ -16,7 +16,7 @@
 // engine unchanged.  The registered read/write callbacks fire
 //   * from the TaLoS-patched record layer when libtlsgpu.so is interposed
 //     (its calls to tls_processing_* bind here), and
-//   * from the engine's own host-delivery paths (engine.cpp: tlsgpu_open_host /
+//   * from the engine's own host-delivery paths (host_paths.cpp: tlsgpu_open_host /
 //     tlsgpu_seal_host, tlsgpu_deliver_host for the batch and wire paths,
 //     tlsgpu_hook_write_streams), with the SSL* the caller associated with each
 //     session (tlsgpu_sessions_set_owner).

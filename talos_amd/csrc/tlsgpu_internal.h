@@ -1,4 +1,4 @@
-// tlsgpu_internal.h — layouts shared by the host engine (engine.cpp) and the
+// tlsgpu_internal.h — layouts shared by the host units (the .cpp files) and the
 // HIP kernels (gcm_kernels.hip, chacha_kernels.hip, session_kernels.hip).
 #pragma once
 #include <hip/hip_runtime.h>
@@ -294,7 +294,7 @@ int launch_bs_ecb(const DevSession* sessions, uint32_t session, int rounds, cons
                   void* d_out, uint32_t nblocks, hipStream_t s);
 int launch_chacha(const BatchArgs& a, bool seal, bool raw, bool rfc, bool old, hipStream_t s);
 
-// Doorbell slot of the persistent EVP server (evp_server.hip, engine.cpp): one
+// Doorbell slot of the persistent EVP server (evp_server.hip, evp_doorbell.cpp): one
 // per calling thread, in pinned host memory, 256 B.  The thread fills the job
 // (the RawJob itself and, when they fit, its nonce and AAD inline), then
 // stores `post` (its next job number); a server workgroup that sees post != the

@@ -3,7 +3,7 @@
 // tests/test_device_affinity.py).
 //
 // libtlsgpu_devstub.so links the engine's unmodified host objects
-// (engine.cpp, group.cpp, talos_hooks.cpp, compiled by talos_amd/Makefile) with
+// (every csrc/*.cpp, compiled by talos_amd/Makefile) with
 // this file instead of libamdhip64 and the kernel objects, so the C ABI runs on
 // a CPU box with TLSGPU_STUB_DEVICES fake GPUs.  Every allocation, stream and
 // event remembers the device that was current on the calling thread when it

@@ -2,7 +2,7 @@
 DESIGN.md §6 "device affinity").
 
 The group split (talos_amd/csrc/group.cpp) and the EVP device spread
-(engine.cpp evp_pick) have only ever run with every member on device 0, where
+(evp_aead.cpp evp_pick) have only ever run with every member on device 0, where
 a missing hipSetDevice cannot show.  Here the engine's unmodified host objects
 run against tests/devstub/devstub.cpp — a recording stand-in for the HIP
 runtime with TLSGPU_STUB_DEVICES fake GPUs (libtlsgpu_devstub.so, CPU only).

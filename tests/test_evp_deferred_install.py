@@ -1,5 +1,5 @@
 """Deferred session install for EVP contexts (round 5; VERDICT r04 next-round 6;
-engine.cpp defer_install, evp_server.hip install / scrub ops).
+evp_aead.cpp defer_install, evp_server.hip install / scrub ops).
 
 With the doorbell on (the round-5 default), EVP_AEAD_CTX_init builds the
 session image on the host (session_host.cpp: the key schedule, H and the GHASH

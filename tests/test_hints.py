@@ -1,6 +1,6 @@
 """Batch-shape hints (tlsgpu_sessions_hint, include/tlsgpu.h): the rule a caller
 applies to a batch it built (talos_amd.batch_hints) matches the engine's own
-host-side rule for host-resident batches (engine.cpp host_hints) and the
+host-side rule for host-resident batches (host_paths.cpp host_hints) and the
 device's kernel selection (pack: nb + 2 <= 64; per-wave sessions: runs x 12 >
 records).  CPU only."""
 import numpy as np

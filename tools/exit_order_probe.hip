@@ -8,7 +8,7 @@
 // it happened in and the library of the callback; each callback is wrapped so
 // that, at exit, the order in which the handlers RUN is printed too.  The
 // program walks the engine's own sequence: runtime init, an engine stream, four
-// call streams, then "the first server" (where engine.cpp registered its exit
+// call streams, then "the first server" (where evp_doorbell.cpp registers its exit
 // handler), two server streams with a spinning kernel each, eight calling
 // threads with thread-local staging — and exits with the servers still
 // spinning.  Our handler reports whether the runtime still answers when it
@@ -121,7 +121,7 @@ static void our_exit_handler() {
   }
 }
 
-struct Staging {  // engine.cpp's thread-local staging, in miniature
+struct Staging {  // evp_internal.h's thread-local staging, in miniature
   uint8_t* d = nullptr;
   uint8_t* h = nullptr;
   hipEvent_t ev = nullptr;

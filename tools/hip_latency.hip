@@ -1,5 +1,5 @@
 // hip_latency.hip — HIP runtime round-trip latencies on this box, the budget
-// of one synchronous EVP call (engine.cpp gpu_call_impl / the EVP queue):
+// of one synchronous EVP call (evp_aead.cpp gpu_call_impl / the EVP queue):
 // empty kernel, small pinned H2D / D2H, event vs stream sync, zero-copy kernel
 // access to pinned host memory, and the same from T concurrent threads.
 // usage: hip_latency [spin]
