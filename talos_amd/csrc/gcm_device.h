@@ -34,10 +34,18 @@ constexpr uint32_t Q_OFF = R4_OFF + 64;      // hybrid kernel: per-run record qu
 constexpr uint32_t DBG_OFF = Q_OFF + 16;     // hybrid kernel: phase counters (diagnostic)
 constexpr uint32_t PLAN_OFF = DBG_OFF + 32 * 8;  // queue kernel: per-run pack plan
 constexpr uint32_t kPlanCap = 2048;                // records planned per run (runs split)
+// Queue kernel: the session's lengths-block table (load_len_table, GhLaneLen),
+// 8 rows of 16 entries: rows p < kLenRows (nibble v at nibble position p of the
+// ciphertext bit count) * H, row kLenRows the TLS AAD bit count * H in every
+// entry, row 7 zero.
+constexpr uint32_t LEN_OFF = PLAN_OFF + 4 * kPlanCap;
+constexpr uint32_t kLenRows = 6;
+constexpr uint32_t kLenEntries = 8 * 16;
+static_assert(8ull * TLSGPU_MAX_RECORD < (1ull << (4 * kLenRows)), "ciphertext bit count nibbles");
 #ifdef TG_LDS_BYTES  // a translation unit with its own LDS plan (gcm_pw.hip)
 constexpr uint32_t LDS_BYTES = TG_LDS_BYTES;
 #else
-constexpr uint32_t LDS_BYTES = PLAN_OFF + 4 * kPlanCap;
+constexpr uint32_t LDS_BYTES = LEN_OFF + 16 * kLenEntries;
 #endif
 
 __shared__ __attribute__((aligned(16))) uint8_t s_lds[LDS_BYTES];
@@ -306,6 +314,13 @@ struct GhLane {
   __device__ __forceinline__ void mul64(const uint32_t x[4], uint32_t o[4]) const;
   __device__ __forceinline__ void shoup(const uint32_t X[4], uint32_t e, uint32_t Z[4]) const;
 };
+
+// GhLane plus the session's lengths-block table at LEN_OFF (load_len_table):
+// the queue kernel's policy.  gcm_finish then takes LEN * H from the table
+// instead of folding the lengths block into a lane chain (gcm_close_len).
+struct GhLaneLen : GhLane {};
+template <class G> inline constexpr bool gh_has_len_table = false;
+template <> inline constexpr bool gh_has_len_table<GhLaneLen> = true;
 
 __device__ __forceinline__ GhLane gh_lane(uint32_t lane) {
   GhLane g;
@@ -651,6 +666,37 @@ __device__ __forceinline__ uint32_t gcm_close_chain(const RecCtx& rc, uint32_t (
   return jlast == -2 ? 0u : (uint32_t)((int32_t)nb + 1 - jlast);
 }
 
+// The same close without the all-lane multiply (policies with a lengths-block
+// table, GhLaneLen).  gcm_close_chain gives lane l* = nb % 64 the value
+// x * H^64 ^ LEN at weight H^1; that is x * H^65 ^ LEN * H, so here lane l*
+// keeps x and takes the weight H^65 (its chain's last element is block
+// nb - 64, or the AAD for nb = 63, or nothing: x = 0), and the caller adds
+// LEN * H (len_term) to the wave sum.  Every other lane is as above.  Kernels
+// whose AAD length varies per job (gcm_raw.h) or that have no room for the
+// table (gcm_pw.hip) keep gcm_close_chain.
+__device__ __forceinline__ uint32_t gcm_close_len(const RecCtx& rc, const uint32_t (&x)[4],
+                                                  uint32_t (&xb)[4], uint32_t lane) {
+  const uint32_t nb = (rc.n + 15) >> 4;
+  be_from_le(x, xb);
+  if (lane == (nb & 63)) return (uint32_t)kPowMax;
+  if (lane < nb) return nb + 1 - (lane + ((nb - 1 - lane) & ~63u));
+  return lane == 63 ? nb + 2 : 0u;  // the AAD alone (j = -1), or an empty chain
+}
+
+// This lane's share of LEN * H, LEN = BE64(13 * 8) || BE64(8 n) (BE words): lane
+// p < kLenRows reads the entry of nibble p of the ciphertext bit count, lane
+// kLenRows an AAD entry, the others a zero entry of row 7 — one ds_read_b128 for
+// the wave; the wave sum of gcm_tag adds the shares up.  Row and nibble go
+// through inline constants only, and the lane through an empty asm: nothing
+// of this is kept in VGPRs across the step loop (lane constants and literals
+// hoisted out of the record loop made the open kernels spill).
+__device__ __forceinline__ uint4 len_term(const RecCtx& rc, uint32_t lane) {
+  asm volatile("" : "+v"(lane));
+  const uint32_t row = min(lane, 7u);
+  const uint32_t nib = ((rc.n * 8u) >> (4u * row)) & 0xFu;
+  return lds_u128(LEN_OFF + ((row << 8) + (nib << 4)));
+}
+
 // Zero n bytes at d (the plaintext of a record whose tag failed,
 // evp_aead.c:137-143): the whole wave, 16-B stores for the aligned bulk (a
 // byte loop made a tampered 16 KiB record's wave 256 store rounds long).
@@ -702,8 +748,15 @@ __device__ __forceinline__ void gcm_finish(const RecCtx& rc, uint32_t (&x)[4], c
                                            const DevSession* __restrict__ S, int32_t* status_slot,
                                            uint32_t lane, const G& gl) {
   uint32_t xb[4], y[4] = {0, 0, 0, 0};
-  const uint32_t e = gcm_close_chain(rc, x, xb, lane, gl);
-  if (e != 0) gl.shoup(xb, e, y);
+  if constexpr (gh_has_len_table<G>) {
+    const uint32_t e = gcm_close_len(rc, x, xb, lane);
+    if (e != 0) gl.shoup(xb, e, y);
+    const uint4 lt = len_term(rc, lane);
+    y[0] ^= lt.x; y[1] ^= lt.y; y[2] ^= lt.z; y[3] ^= lt.w;
+  } else {
+    const uint32_t e = gcm_close_chain(rc, x, xb, lane, gl);
+    if (e != 0) gl.shoup(xb, e, y);
+  }
   gcm_tag<SEAL>(rc, y, ek0, S, status_slot, lane);
 }
 
@@ -1295,6 +1348,48 @@ __device__ void load_session_tables(const DevGcmTables* __restrict__ tab) {
   const uint4* sh = reinterpret_cast<const uint4*>(&tab->shoup[0][0][0]);
   for (uint32_t k = threadIdx.x; k < kPowMax * 16; k += NT)  // k = 16 (e - 1) + v
     *reinterpret_cast<uint4*>(s_lds + sh_base(1 + (k >> 4)) + (k & 15u) * 256u) = sh[k];
+}
+
+// The session's lengths-block table (LEN_OFF, read by len_term), BE words:
+// entry 16 p + v is (nibble v at nibble p of the ciphertext bit count) * H for
+// p < kLenRows, BE64(13 * 8) * H (the TLS AAD of parse_tls) for p = kLenRows,
+// zero for p = 7.  With T[v] the H^1 Shoup entries and s() the 4-bit shift of
+// mul_shoup, X * H is the Horner sum z = s(z) ^ T[nibble k] over X's nibbles
+// k = 0..31 (k = 0: the low nibble of byte 15), so a nibble v alone at k gives
+// s^(31 - k)(T[v]).  Reads the table in global memory, so it needs no barrier
+// after load_session_tables' copy; the last two waves take it (the first
+// have two entries of that copy each).
+template <int NT>
+__device__ void load_len_table(const DevGcmTables* __restrict__ tab) {
+  constexpr uint32_t ab = 13 * 8;  // AAD bits: nibble k = 16 is ab & 15, k = 17 is ab >> 4
+  static_assert(ab < 256, "two nibbles");
+  static_assert(NT >= (int)kLenEntries, "one entry per thread");
+  const uint4* sh = reinterpret_cast<const uint4*>(&tab->shoup[0][0][0]);
+  // the entry index through an empty asm: what derives from it is computed
+  // here, once per run, not hoisted out of the caller's run loop into VGPRs
+  // that the record loop then lacks
+  uint32_t i = NT - 1 - threadIdx.x;
+  asm volatile("" : "+v"(i));
+  if (i >= kLenEntries) return;
+  const uint32_t p = i >> 4;
+  const bool aad = p == kLenRows;
+  const uint32_t k = aad ? 17u : p;
+  uint4 z = sh[aad ? ab >> 4 : i & 15u];
+  auto shift = [](uint4& v) {
+    const uint32_t rem = v.w & 0xF;
+    v.w = __builtin_amdgcn_alignbit(v.z, v.w, 4);
+    v.z = __builtin_amdgcn_alignbit(v.y, v.z, 4);
+    v.y = __builtin_amdgcn_alignbit(v.x, v.y, 4);
+    v.x = (v.x >> 4) ^ rem4(rem);
+  };
+  if (aad) {
+    uint4 u = sh[ab & 15u];
+    shift(u);
+    z.x ^= u.x; z.y ^= u.y; z.z ^= u.z; z.w ^= u.w;
+  }
+  for (uint32_t s = k; s < 31; s++) shift(z);
+  if (p > kLenRows) z = make_uint4(0, 0, 0, 0);
+  *reinterpret_cast<uint4*>(s_lds + LEN_OFF + 16u * i) = z;
 }
 
 // Bitsliced round-key masks from the round-key words (SGPRs): s_bfe_i32

@@ -332,10 +332,12 @@ __device__ __forceinline__ RecConsts rec_consts_fresh(const RecPre* p) {
   return rc;
 }
 
-template <bool SEAL, int ROUNDS, int NB = 4>
+// G: GhLaneLen from the queue kernel (it builds the run's lengths-block table),
+// GhLane from kernels that do not (experimental/gcm_fused.h).
+template <bool SEAL, int ROUNDS, int NB = 4, class G = GhLane>
 __device__ __forceinline__ void hy_tt_record(const BatchArgs& a, const RecPre* __restrict__ pre,
                                              uint32_t r, const DevSession* __restrict__ S,
-                                             uint32_t lane, uint32_t laneoff, const GhLane& gl) {
+                                             uint32_t lane, uint32_t laneoff, const G& gl) {
   const tlsgpu_record* D = reinterpret_cast<const tlsgpu_record*>(a.descs);
   RecCtx rc;
   const tlsgpu_record d = load_desc(D + r);
@@ -811,7 +813,7 @@ __global__ __launch_bounds__(NT, 1) void gcm_hy_kernel(BatchArgs a,
   const uint32_t lane = threadIdx.x & 63;
   const uint32_t wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   const uint32_t laneoff = aes_laneoff(lane);
-  const GhLane gl = gh_lane(lane);
+  const GhLaneLen gl{gh_lane(lane)};  // + the run's lengths-block table
   const tlsgpu_record* D = reinterpret_cast<const tlsgpu_record*>(a.descs);
   const bool bs_role = wave < (uint32_t)BSW;
   if (BSW && !bs_role) __builtin_amdgcn_s_setprio(1);
@@ -961,7 +963,10 @@ __global__ __launch_bounds__(NT, 1) void gcm_hy_kernel(BatchArgs a,
       __syncthreads();  // every wave is done with the previous run (queue, tables, plan)
       pc.lap(bs_role ? 4 : 12, lane);
       if (threadIdx.x == 0) *q = pos;
-      if (sid != cur) load_session_tables<NT>(a.gcm_tables + sid);
+      if (sid != cur) {
+        load_session_tables<NT>(a.gcm_tables + sid);
+        load_len_table<NT>(a.gcm_tables + sid);
+      }
       cur = sid;
       const uint32_t run_len = run_end - pos;
       if (has_short) {  // the plan: greedy pack from every start, <= 64 lanes, <= 32 records
