@@ -970,6 +970,16 @@ struct PhaseClock {
     }
   }
 };
+// A lap on a clock the caller may not have (hand-over slots 0, 7, 8: the queue
+// kernel's no-pack variants without a bitsliced role pass one, started before
+// the plain claim; the pack variants and the other callers none).
+__device__ __forceinline__ void lap_if(PhaseClock* c, int i, uint32_t lane) {
+  if (c) c->lap(i, lane);
+}
+// Slots of the hand-over interval (queue kernel, T-table role)
+constexpr int kLapDesc = 0;    // claim -> descriptor arrived
+constexpr int kLapConsts = 7;  // descriptor -> bounds, parse, RecPre constants ready
+constexpr int kLapFirst = 8;   // constants ready -> first group's loads issued, AES next
 
 // ---------------------------------------------------------------------------
 // NB-block T-table keystream (the hybrid kernel's T-table waves run alone on
@@ -1039,15 +1049,27 @@ __device__ __forceinline__ void aes_ctr16xN(uint32_t (&ks)[NB][4], const uint32_
 
 // Full NB-step groups of a record (any alignment) from block `start` on (FAST
 // constants only): NB keystream blocks per lane in flight, the next group's
-// input loads issued first, and the GHASH of each group's NB blocks folded
-// into the AES rounds of the following group (the chain's LDS round trips then
-// overlap the AES lookups instead of trailing them).  Advances `start` past
-// the groups done; the caller finishes the record with gcm_blocks.
-template <bool SEAL, int ROUNDS, int NB, class G>
+// input loads issued first, and the GHASH of NB blocks folded into the AES
+// rounds (the chain's LDS round trips then overlap the AES lookups instead of
+// trailing them).  GHASH runs over ciphertext:
+//   * seal, and open without OWN: each group's blocks (gp) are hashed in the
+//     rounds of the following group, step b after round 3 + 2b; the first
+//     group runs without the hook and the last group's NB steps follow the
+//     loop (seal's ciphertext is the output; open without OWN is the same
+//     order, kept where the other order was measured slower: DESIGN.md §4.1);
+//   * open with OWN: the ciphertext is the input, in c[b] before the group's
+//     AES starts, so every group — the first included — hashes its own blocks
+//     in its own rounds; nothing is carried to the next group and no GHASH
+//     step follows the loop.  A record's first group (its ciphertext loads
+//     were issued just before) takes step b after round FR0 + FRS * b, so a
+//     caller can put the wave's wait for those loads some rounds later.
+// Advances `start` past the groups done; the caller finishes the record with
+// gcm_blocks.
+template <bool SEAL, int ROUNDS, int NB, class G, bool OWN = false, int FR0 = 3, int FRS = 2>
 __device__ __forceinline__ void gcm_blocks_xN(const RecCtx& rc, const DevSession* __restrict__ S,
                                               const RecConsts& rcc, uint32_t (&x)[4],
                                               uint32_t& start, uint32_t lane, uint32_t laneoff,
-                                              const G& gl) {
+                                              const G& gl, PhaseClock* hc = nullptr) {
   const bool aligned = ((((uintptr_t)rc.src) | ((uintptr_t)rc.dst)) & 15) == 0;
 #ifndef TG_XN_UNALIGNED
   if (!aligned) return;
@@ -1059,22 +1081,32 @@ __device__ __forceinline__ void gcm_blocks_xN(const RecCtx& rc, const DevSession
   const uint32_t nfull_steps = (rc.n >> 4) / kWave;
   uint32_t t = start / kWave;
   if (t + NB > nfull_steps) return;
-  uint32_t c[NB][4], gp[NB][4];
+  constexpr bool kLateGh = SEAL || !OWN;  // hash a group in the next group's rounds
+  uint32_t c[NB][4];
+  [[maybe_unused]] uint32_t gp[NB][4];  // the previous group's ciphertext (kLateGh)
 #pragma unroll
   for (int b = 0; b < NB; b++) load_block(rc.src + 16u * (start + kWave * b + lane), 16, aligned, c[b]);
   auto ghash_step = [&](int b) {
     uint32_t xk[4];
     gl.mul64(x, xk);
-    x[0] = xk[0] ^ gp[b][0]; x[1] = xk[1] ^ gp[b][1]; x[2] = xk[2] ^ gp[b][2]; x[3] = xk[3] ^ gp[b][3];
+    const uint32_t(&g)[4] = kLateGh ? gp[b] : c[b];  // own rounds: the group's own input
+    x[0] = xk[0] ^ g[0]; x[1] = xk[1] ^ g[1]; x[2] = xk[2] ^ g[2]; x[3] = xk[3] ^ g[3];
   };
-  // GHASH step b of the previous group after AES round 3 + 2b (all NB steps
-  // fall inside rounds 3 .. ROUNDS-1)
+  // all NB steps fall inside rounds 3 .. ROUNDS-1 (aes_ctr16xN calls the hook there)
   static_assert(3 + 2 * (NB - 1) < ROUNDS, "GHASH steps must fit between the AES rounds");
+  static_assert(FR0 >= 3 && FRS >= 1 && FR0 + FRS * (NB - 1) < ROUNDS,
+                "the first group's GHASH steps must fit between the AES rounds");
   auto hook = [&](int r) {
 #pragma unroll
     for (int b = 0; b < NB; b++)
       if (r == 3 + 2 * b) ghash_step(b);
   };
+  [[maybe_unused]] auto hook_first = [&](int r) {
+#pragma unroll
+    for (int b = 0; b < NB; b++)
+      if (r == FR0 + FRS * b) ghash_step(b);
+  };
+  lap_if(hc, kLapFirst, lane);  // the first group's loads are issued, not waited for
   bool first = true;
   for (; t + NB <= nfull_steps; t += NB, start += NB * kWave) {
     const uint32_t i = start + lane;
@@ -1086,33 +1118,45 @@ __device__ __forceinline__ void gcm_blocks_xN(const RecCtx& rc, const DevSession
     uint32_t ctr[NB], k[NB][4];
 #pragma unroll
     for (int b = 0; b < NB; b++) ctr[b] = ctr0 + i + kWave * b;
-    if (first)
-      aes_ctr16xN<NB, ROUNDS>(k, ctr, rcc, rk03, rk, rkr, laneoff);
-    else
+    // a record's first group: no hook (nothing to hash yet), or its own rounds
+    if (first) {
+      if constexpr (kLateGh)
+        aes_ctr16xN<NB, ROUNDS>(k, ctr, rcc, rk03, rk, rkr, laneoff);
+      else
+        aes_ctr16xN<NB, ROUNDS>(k, ctr, rcc, rk03, rk, rkr, laneoff, hook_first);
+    } else {
       aes_ctr16xN<NB, ROUNDS>(k, ctr, rcc, rk03, rk, rkr, laneoff, hook);
+    }
     first = false;
 #pragma unroll
     for (int b = 0; b < NB; b++) {
       uint32_t o[4] = {c[b][0] ^ k[b][0], c[b][1] ^ k[b][1], c[b][2] ^ k[b][2], c[b][3] ^ k[b][3]};
       store_block(rc.dst + 16u * (i + kWave * b), 16, aligned, o);
+      if constexpr (kLateGh) {
 #pragma unroll
-      for (int w = 0; w < 4; w++) gp[b][w] = SEAL ? o[w] : c[b][w];
+        for (int w = 0; w < 4; w++) gp[b][w] = SEAL ? o[w] : c[b][w];
+      }
     }
 #pragma unroll
     for (int b = 0; b < NB; b++)
 #pragma unroll
       for (int w = 0; w < 4; w++) c[b][w] = nx[b][w];
   }
+  if constexpr (kLateGh) {
 #pragma unroll
-  for (int b = 0; b < NB; b++) ghash_step(b);  // the last group's GHASH
+    for (int b = 0; b < NB; b++) ghash_step(b);  // the last group's GHASH
+  }
 }
 
 // gcm_record<SEAL, ROUNDS, true> with the NB-wide full-block loop first.
-template <bool SEAL, int ROUNDS, int NB = 4, class G = GhLane>
+// OWN: open hashes each group in its own AES rounds, a record's first group
+// one round apart with the last step after round ROUNDS - 2 (the queue
+// kernel's no-pack variants).
+template <bool SEAL, int ROUNDS, int NB = 4, class G = GhLane, bool OWN = false>
 __device__ void gcm_record_x4(const RecCtx& rc, const DevSession* __restrict__ S,
                               const RecConsts& rcc, int32_t* status_slot, uint32_t lane,
                               uint32_t laneoff, const G& gl,
-                              unsigned long long* dbg = nullptr) {
+                              unsigned long long* dbg = nullptr, PhaseClock* hc = nullptr) {
   PhaseClock pc(dbg);
   uint32_t x[4] = {0, 0, 0, 0};
   if (rc.aad_len != 0 && lane == 63) {
@@ -1120,7 +1164,8 @@ __device__ void gcm_record_x4(const RecCtx& rc, const DevSession* __restrict__ S
     x[2] = bswap32(rc.aad_be[2]); x[3] = bswap32(rc.aad_be[3]);
   }
   uint32_t start = 0;
-  gcm_blocks_xN<SEAL, ROUNDS, NB>(rc, S, rcc, x, start, lane, laneoff, gl);
+  gcm_blocks_xN<SEAL, ROUNDS, NB, G, OWN, OWN ? ROUNDS - 1 - NB : 3, OWN ? 1 : 2>(
+      rc, S, rcc, x, start, lane, laneoff, gl, hc);
 #ifdef TG_XN_ODD_STEP
   // an odd full step left by the NB-wide loop: the pipelined one-step loop
   if (NB > 1) gcm_blocks_xN<SEAL, ROUNDS, 1>(rc, S, rcc, x, start, lane, laneoff, gl);
@@ -1299,10 +1344,17 @@ __device__ void fill_aes_lds() {
 
 // Expand the session's 128 basis vectors K*x^p into T[j][b] and copy the
 // Shoup tables of H^1..H^65.
-template <int NT>
+// OPAQUE (the queue kernel): the thread index goes through an empty asm, as in
+// load_len_table, so the byte masks and the lane's copy address are computed
+// here, once per session change, and not hoisted out of the caller's run loop
+// into VGPRs that the record loop then lacks (they were that kernel's spilled
+// values).  The other callers keep the plain index and their code.
+template <int NT, bool OPAQUE = false>
 __device__ void load_session_tables(const DevGcmTables* __restrict__ tab) {
-  const uint32_t bl = threadIdx.x & 63;
-  for (uint32_t jj = threadIdx.x >> 6; jj < 16; jj += NT / kWave) {
+  uint32_t tid = threadIdx.x;
+  if constexpr (OPAQUE) asm volatile("" : "+v"(tid));
+  const uint32_t bl = tid & 63;
+  for (uint32_t jj = tid >> 6; jj < 16; jj += NT / kWave) {
     const uint32_t j = __builtin_amdgcn_readfirstlane(jj);  // byte position
     uint32_t lo[4] = {0, 0, 0, 0};
 #ifdef TG_VECTOR_SESSION_LOADS
@@ -1346,7 +1398,7 @@ __device__ void load_session_tables(const DevGcmTables* __restrict__ tab) {
     }
   }
   const uint4* sh = reinterpret_cast<const uint4*>(&tab->shoup[0][0][0]);
-  for (uint32_t k = threadIdx.x; k < kPowMax * 16; k += NT)  // k = 16 (e - 1) + v
+  for (uint32_t k = tid; k < kPowMax * 16; k += NT)  // k = 16 (e - 1) + v
     *reinterpret_cast<uint4*>(s_lds + sh_base(1 + (k >> 4)) + (k & 15u) * 256u) = sh[k];
 }
 

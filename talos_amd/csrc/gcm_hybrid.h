@@ -334,13 +334,18 @@ __device__ __forceinline__ RecConsts rec_consts_fresh(const RecPre* p) {
 
 // G: GhLaneLen from the queue kernel (it builds the run's lengths-block table),
 // GhLane from kernels that do not (experimental/gcm_fused.h).
-template <bool SEAL, int ROUNDS, int NB = 4, class G = GhLane>
+template <bool SEAL, int ROUNDS, int NB = 4, class G = GhLane, bool OWN = false>
 __device__ __forceinline__ void hy_tt_record(const BatchArgs& a, const RecPre* __restrict__ pre,
                                              uint32_t r, const DevSession* __restrict__ S,
-                                             uint32_t lane, uint32_t laneoff, const G& gl) {
+                                             uint32_t lane, uint32_t laneoff, const G& gl,
+                                             PhaseClock* hc = nullptr) {
   const tlsgpu_record* D = reinterpret_cast<const tlsgpu_record*>(a.descs);
   RecCtx rc;
   const tlsgpu_record d = load_desc(D + r);
+  if (hc && hc->dbg) {  // phase timing: the lap waits for the descriptor
+    asm volatile("" ::"s"(d.len_type));
+    hc->lap(kLapDesc, lane);
+  }
   // fused: an out-of-bounds record's status was written by the prologue
   if (a.fused && !rec_in_bounds(d, S, a.in_bytes, a.out_bytes, SEAL)) return;
   if (!parse_tls<SEAL>(d, S, a.in, a.out, a.status + r, lane, rc)) return;
@@ -352,7 +357,11 @@ __device__ __forceinline__ void hy_tt_record(const BatchArgs& a, const RecPre* _
   }
 #endif
   const RecConsts rcc = rec_consts_fresh(pre + r);
-  gcm_record_x4<SEAL, ROUNDS, NB>(rc, S, rcc, a.status + r, lane, laneoff, gl, a.dbg);
+  if (hc && hc->dbg) {  // phase timing: the lap waits for the constants
+    asm volatile("" ::"s"(rcc.k2[3]));
+    hc->lap(kLapConsts, lane);
+  }
+  gcm_record_x4<SEAL, ROUNDS, NB, G, OWN>(rc, S, rcc, a.status + r, lane, laneoff, gl, a.dbg, hc);
 }
 
 // Packed bitsliced wave role: a record of a_min..16384
@@ -810,6 +819,12 @@ __global__ __launch_bounds__(NT, 1) void gcm_hy_kernel(BatchArgs a,
     // hints) only the pack variant is launched
     return;
   }
+  // the no-pack variants only: open's GHASH in each group's own rounds, and the
+  // session-table constants kept out of the record loop's VGPRs.  In the pack
+  // variants either one made config D slower, so those keep
+  // the order and the tables code they had.
+  constexpr bool kOwnRounds = !PACK;
+  constexpr bool kOpaqueTables = !PACK;
   const uint32_t lane = threadIdx.x & 63;
   const uint32_t wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   const uint32_t laneoff = aes_laneoff(lane);
@@ -964,7 +979,7 @@ __global__ __launch_bounds__(NT, 1) void gcm_hy_kernel(BatchArgs a,
       pc.lap(bs_role ? 4 : 12, lane);
       if (threadIdx.x == 0) *q = pos;
       if (sid != cur) {
-        load_session_tables<NT>(a.gcm_tables + sid);
+        load_session_tables<NT, kOpaqueTables>(a.gcm_tables + sid);
         load_len_table<NT>(a.gcm_tables + sid);
       }
       cur = sid;
@@ -1042,6 +1057,12 @@ __global__ __launch_bounds__(NT, 1) void gcm_hy_kernel(BatchArgs a,
             if (rb < run_end) hy_tt_record<SEAL, ROUNDS, NB>(a, pre, rb, S, lane, laneoff, gl);
           }
         } else {
+          // hand-over slots 0, 7, 8: started before the claim; only where
+          // every T-table claim is the plain one below (no packs, no
+          // bitsliced or B16W role), so the slots time one path and the pack
+          // variants' code stays what it was
+          constexpr bool kHandoverLaps = !PACK && BSW == 0 && B16W == 0;
+          PhaseClock hc(kHandoverLaps ? a.dbg : nullptr);
           uint32_t r;
           if (B16W > 0 && b16_role) {
             r = queue_take(q, 1, lane);
@@ -1092,7 +1113,8 @@ __global__ __launch_bounds__(NT, 1) void gcm_hy_kernel(BatchArgs a,
             else __builtin_amdgcn_s_setprio(1);
           }
 #endif
-          hy_tt_record<SEAL, ROUNDS, NB>(a, pre, r, S, lane, laneoff, gl);
+          hy_tt_record<SEAL, ROUNDS, NB, GhLaneLen, kOwnRounds>(a, pre, r, S, lane, laneoff, gl,
+                                                               kHandoverLaps ? &hc : nullptr);
 #ifndef TG_NO_TAIL_PRIO
           if (!BSW && !PACK) __builtin_amdgcn_s_setprio(0);
 #endif
