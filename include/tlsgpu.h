@@ -1,5 +1,7 @@
 /*
- * tlsgpu.h — MI355X-native TLS 1.2 record bulk-cipher engine: batch C ABI.
+ * tlsgpu.h — MI355X-native TLS record bulk-cipher engine: batch C ABI
+ * (TLS 1.2 AEAD records as LibreSSL 2.4.1 protects them, and TLS 1.3 AES-GCM
+ * records, RFC 8446 5.2-5.4: see "TLS 1.3 sessions" below).
  *
  * This is the GPU extension that sits beside the drop-in EVP_AEAD ABI
  * (include/tlsgpu_evp.h).  It has no reference counterpart; it batches the
@@ -65,6 +67,10 @@ enum tlsgpu_aead {
  * output span (out_off, plaintext / fragment length) leaves d_in / d_out as
  * sized by the caller; nothing of the record was read or written. */
 #define TLSGPU_REC_OUT_OF_BOUNDS (-5)
+/* TLS 1.3 open only: the tag verified but the decrypted TLSInnerPlaintext is
+ * empty or all zero, so it carries no content type (RFC 8446 5.4:
+ * unexpected_message).  The output region stays as decrypted. */
+#define TLSGPU_REC_NO_CONTENT_TYPE (-6)
 
 /* Largest plaintext per record the batch kernels accept: 65534 AES blocks, so
  * GCM counters 2..nb+1 stay below 2^16 (TLS records are <= 16 KiB + 2 KiB,
@@ -79,7 +85,29 @@ enum tlsgpu_aead {
  * seal: in_off -> plaintext, length = plaintext length; the fragment
  *       (explicit nonce || ct || tag) is written at out_off (t1_enc.c:898-914).
  * seq is the record's 64-bit sequence number (read_sequence/write_sequence
- * before tls1_record_sequence_increment, t1_enc.c:258-266,841-847). */
+ * before tls1_record_sequence_increment, t1_enc.c:258-266,841-847).
+ *
+ * TLS 1.3 sessions (version 0x0304, AES-GCM; RFC 8446 5.2-5.4).  The record
+ * nonce is fixed_iv(12) XOR (0^32 || BE64(seq)), there is no explicit nonce,
+ * and the AAD is the record header 0x17 0x03 0x03 BE16(ciphertext length with
+ * the tag); the descriptor's type bits do not enter it.
+ * seal: in_off / length are the content and the type bits the INNER content
+ *       type.  The engine encrypts content || type (no padding: a padding policy
+ *       is out of scope, as with LibreSSL's and OpenSSL's defaults) and writes
+ *       ciphertext || tag(16) at out_off; status = length + 1 + 16.  The type
+ *       byte is synthesized: d_in is never read past in_off + length.
+ * open: length is the fragment, ciphertext || tag.  The decrypted
+ *       TLSInnerPlaintext (length - 16 bytes, its zero padding included) is
+ *       written at out_off (in place: out_off = in_off).  status = the CONTENT
+ *       length, i.e. the index of the last non-zero byte; the inner content
+ *       type is the byte at out_off + status.  TLSGPU_REC_NO_CONTENT_TYPE: the
+ *       tag verified but the inner plaintext is empty or all zero (region as
+ *       decrypted).  TLSGPU_REC_BAD_MAC zero-fills all length - 16 bytes;
+ *       length < 16 gives TLSGPU_REC_PUBLIC_INVALID.
+ * TLSGPU_MAX_RECORD bounds the inner plaintext, and the bounds rule of
+ * TLSGPU_REC_OUT_OF_BOUNDS uses these spans.  Limits: no ChaCha20-Poly1305, no
+ * padding on seal, post-handshake records only (the compatibility
+ * ChangeCipherSpec of a handshake is the caller's to skip). */
 typedef struct tlsgpu_record {
 	uint64_t in_off;
 	uint64_t out_off;
@@ -96,12 +124,23 @@ typedef struct tlsgpu_session_params {
 	int32_t aead;			/* enum tlsgpu_aead */
 	uint32_t key_len;		/* 16 or 32 */
 	uint8_t key[32];
-	uint32_t fixed_iv_len;		/* 4 (GCM), 12 (ChaCha), 0 (ChaCha old) */
+	uint32_t fixed_iv_len;		/* 4 (GCM), 12 (ChaCha, TLS 1.3 GCM), 0 (ChaCha old) */
 	uint8_t fixed_iv[12];
 	uint32_t tag_len;		/* 0 = default 16 (EVP_AEAD_DEFAULT_TAG_LENGTH) */
-	uint16_t version;		/* s->version, e.g. 0x0303 */
+	uint16_t version;		/* s->version, e.g. 0x0303; 0x0304: a TLS 1.3 session */
 	uint16_t reserved;
 } tlsgpu_session_params;
+/* A TLS 1.3 session is aead = TLSGPU_AES_128_GCM / _256_GCM, version = 0x0304,
+ * fixed_iv_len = 12 (the traffic secret's write IV; the key is its write key,
+ * and seq starts at 0 for every key), tag_len 16 (0 means 16).  0x0304 with
+ * any other fixed_iv_len, tag_len or with a ChaCha kind is TLSGPU_EINVAL at
+ * install.  Every other version behaves as before.
+ * One session table holds one generation: the GCM kernels are compiled once
+ * per record layout (carrying the layout as per-session data cost the TLS 1.2
+ * queue kernel's pack variants spilled registers), so the
+ * first install fixes whether a table is TLS 1.3 or not, and an install of the
+ * other generation returns TLSGPU_EINVAL.  A server keeps one table per
+ * generation; batches of the two run side by side on their own streams. */
 
 typedef struct tlsgpu_engine tlsgpu_engine;
 typedef struct tlsgpu_sessions tlsgpu_sessions;
@@ -147,7 +186,9 @@ int tlsgpu_seal_batch(tlsgpu_sessions *t, const tlsgpu_record *d_recs, uint32_t 
  * A caller that knows its batches rules them out:
  *   TLSGPU_HINT_NO_SHORT_RECORDS  no GCM record of <= 62 blocks (open: length
  *                                 <= 1,016 B with the 8-B explicit nonce and a
- *                                 16-B tag): the pack variant is not launched;
+ *                                 16-B tag; TLS 1.3: 62 blocks of inner
+ *                                 plaintext, seal length <= 991 B, open length
+ *                                 <= 1,008 B): the pack variant is not launched;
  *   TLSGPU_HINT_SESSION_RUNS      records come in session runs of >= 12
  *                                 records on average: the per-wave-session
  *                                 kernel is not launched.
@@ -177,7 +218,9 @@ int tlsgpu_sessions_hint(tlsgpu_sessions *t, unsigned hints);
  * records' plaintext spans (from the first span to the last, or all of
  * out_bytes when the layout does not ascend) come back as zeros out of place;
  * in place, the headers, explicit nonces and tags are written back unchanged.
- * Bytes outside that range are not touched. */
+ * Bytes outside that range are not touched.  TLS 1.3 tables: spans, statuses
+ * and the read hook follow the TLS 1.3 rules above (the hook sees the content,
+ * status bytes; the inner type follows it in h_out). */
 int tlsgpu_open_host(tlsgpu_sessions *t, const tlsgpu_record *h_recs, uint32_t n,
     const uint8_t *h_in, size_t in_bytes, uint8_t *h_out, size_t out_bytes, int32_t *h_status);
 /* The write direction: plaintext records in host memory (h_in) sealed into
@@ -313,7 +356,16 @@ int tlsgpu_group_sync(tlsgpu_group *g);
  *
  * max_records bounds d_recs / d_status; streams whose records do not fit are
  * truncated at a record boundary (their `records`/`consumed` say how far).
- * d_total receives the number of descriptors written.  Asynchronous. */
+ * d_total receives the number of descriptors written.  Asynchronous.
+ *
+ * Streams of a TLS 1.3 table (the caller passes version = 0x0303, the legacy
+ * record version): the outer type must be 23, else unexpected_message (10); a
+ * fragment above 16384 + 256 B gives record_overflow (22), one below 16 B
+ * decryption_failed (21); records are opened in place at the fragment start.
+ * Then, in order: TLSGPU_REC_NO_CONTENT_TYPE ends the stream with alert 10, a
+ * content length above 16384 with TLSGPU_REC_OVERFLOW and alert 22; for
+ * delivered records the inner content type replaces the type bits of
+ * d_recs[i].len_type, so alerts and handshake records look as in TLS 1.2. */
 #define TLSGPU_WIRE_FIRST_PACKET 1u	/* s->first_packet: accept any version */
 typedef struct tlsgpu_wire_stream {
 	uint64_t wire_off;	/* first byte of the stream in d_wire */
@@ -354,7 +406,11 @@ int tlsgpu_open_wire(tlsgpu_sessions *t, const tlsgpu_wire_stream *d_streams,
  * streams that do not fit max_records are cut at a record boundary) and a
  * status each.  data_bytes / wire_bytes bound the buffers
  * (TLSGPU_REC_OUT_OF_BOUNDS).  tlsgpu_seal_wire_size gives a stream's wire
- * bytes.  Asynchronous. */
+ * bytes.  Asynchronous.
+ * A TLS 1.3 session: each fragment (<= max_fragment <= 16384) goes out as the
+ * header 17 03 03 BE16(len + 17) and ciphertext(content || type) || tag, with
+ * stream.type as the inner type; next_seq and wire_len follow that framing
+ * (tlsgpu_seal_wire_size_v). */
 typedef struct tlsgpu_write_stream {
 	uint64_t data_off;	/* application data at d_data + data_off */
 	uint64_t wire_off;	/* the stream's records go to d_wire + wire_off */
@@ -383,6 +439,11 @@ int tlsgpu_seal_wire(tlsgpu_sessions *t, const tlsgpu_write_stream *d_streams,
  * (8 for GCM, 0 for ChaCha) + fragment + tag_len bytes (0 when len == 0). */
 uint64_t tlsgpu_seal_wire_size(int aead, uint32_t data_len, uint32_t max_fragment,
     uint32_t tag_len);
+/* The same for a session of `version`: 0x0304 with an AES-GCM kind is TLS 1.3
+ * framing, ceil(len / frag) records of 5 + fragment + 1 (inner type) + 16;
+ * anything else is tlsgpu_seal_wire_size. */
+uint64_t tlsgpu_seal_wire_size_v(int aead, uint16_t version, uint32_t data_len,
+    uint32_t max_fragment, uint32_t tag_len);
 
 /* GCM TLS batch kernel selection (process-wide; results are identical).
  * TLSGPU_GCM_AUTO (default): TLSGPU_GCM_SPLIT for batches of at most two

@@ -1,4 +1,6 @@
-"""talos_amd — MI355X-native TLS 1.2 record bulk-cipher engine (Python host side).
+"""talos_amd — MI355X-native TLS record bulk-cipher engine (Python host side):
+TLS 1.2 AEAD records and TLS 1.3 AES-GCM records (``SessionParams(...,
+version=0x0304)`` with the 12-byte write IV; include/tlsgpu.h).
 
 The engine itself is ``libtlsgpu.so`` (HIP kernels for gfx950 behind a C ABI,
 ``include/tlsgpu.h`` + the drop-in EVP_AEAD ABI ``include/tlsgpu_evp.h``).
@@ -61,6 +63,8 @@ WRITE_RESULT_DTYPE = np.dtype([("first", "<u4"), ("records", "<u4"), ("wire_len"
                                ("next_seq", "<u8"), ("reserved", "<u8")])
 assert WRITE_STREAM_DTYPE.itemsize == 40 and WRITE_RESULT_DTYPE.itemsize == 32
 REC_BAD_MAC, REC_PUBLIC_INVALID, REC_SKIPPED, REC_OVERFLOW, REC_OUT_OF_BOUNDS = -1, -2, -3, -4, -5
+REC_NO_CONTENT_TYPE = -6  # TLS 1.3 open: the inner plaintext is empty or all zero
+TLS13_VERSION = 0x0304    # SessionParams.version of a TLS 1.3 session
 
 RECORD_DTYPE = np.dtype([("in_off", "<u8"), ("out_off", "<u8"), ("seq", "<u8"),
                          ("session", "<u4"), ("len_type", "<u4")])
@@ -142,6 +146,7 @@ def load_library(path: str = LIBPATH) -> C.CDLL:
         "tlsgpu_seal_wire": (i32, [vp, vp, u32, vp, C.c_size_t, vp, C.c_size_t, u32, vp, vp, vp,
                                    vp, vp]),
         "tlsgpu_seal_wire_size": (u64, [i32, u32, u32, u32]),
+        "tlsgpu_seal_wire_size_v": (u64, [i32, C.c_uint16, u32, u32, u32]),
         "tlsgpu_host_pipeline": (i32, [vp, C.c_uint, C.c_size_t]),
         "tlsgpu_seal_host": (i32, [vp, vp, u32, vp, C.c_size_t, vp, C.c_size_t, vp]),
         "tlsgpu_sessions_set_owner": (i32, [vp, u32, u32, vp]),
@@ -396,15 +401,18 @@ class SessionTable:
 HINT_NO_SHORT_RECORDS, HINT_SESSION_RUNS = 1, 2
 
 
-def batch_hints(lengths, sessions, seal: bool) -> int:
+def batch_hints(lengths, sessions, seal: bool, tls13: bool = False) -> int:
     """The hints a caller that built the batch can state (tlsgpu.h): no GCM
     record short enough for a pack, session runs of >= 12 records on average.
     `lengths` are the descriptors' length fields, as the engine's host_hints
     reads them: fragment lengths (explicit nonce + ciphertext + tag) for an
-    open, plaintext lengths for a seal."""
+    open, plaintext lengths for a seal.  tls13: 62 blocks of inner plaintext
+    (content + type byte) without an explicit nonce."""
     lengths = np.asarray(lengths)
     sessions = np.asarray(sessions)
     short_max = 992 if seal else 992 + 8 + 16
+    if tls13:
+        short_max = 991 if seal else 992 + 16
     h = 0
     if len(lengths) and int(lengths.min()) > short_max:
         h |= HINT_NO_SHORT_RECORDS
@@ -486,8 +494,14 @@ def seal_wire(table: SessionTable, d_streams: int, n_streams: int, d_data: int, 
                                       d_results, d_total, stream), "tlsgpu_seal_wire")
 
 
-def seal_wire_size(aead: int, data_len: int, max_fragment: int = 0, tag_len: int = 0) -> int:
-    return int(load_library().tlsgpu_seal_wire_size(aead, data_len, max_fragment, tag_len))
+def seal_wire_size(aead: int, data_len: int, max_fragment: int = 0, tag_len: int = 0,
+                   version: int | None = None) -> int:
+    """Wire bytes of one tlsgpu_seal_wire stream; version=0x0304: TLS 1.3 framing
+    (tlsgpu_seal_wire_size_v)."""
+    if version is None:
+        return int(load_library().tlsgpu_seal_wire_size(aead, data_len, max_fragment, tag_len))
+    return int(load_library().tlsgpu_seal_wire_size_v(aead, version, data_len, max_fragment,
+                                                      tag_len))
 
 
 def open_host(table: SessionTable, h_recs: int, n: int, h_in: int, in_bytes: int, h_out: int,

@@ -28,10 +28,15 @@ class RecordBatch:
     entries: list of (session_id, seq, content_type, payload_bytes, kind).
     For ``mode='seal'`` payload is plaintext; for ``mode='open'`` it is the
     record fragment (explicit nonce || ct || tag for GCM).
+
+    ``tls13=True``: the entries belong to a TLS 1.3 session table
+    (include/tlsgpu.h): no explicit nonce, a seal's output is content + inner
+    type + tag (``content_type`` is the inner type) and an open's the whole
+    inner plaintext, fragment - tag.  The default is the TLS 1.2 layout.
     """
 
     def __init__(self, engine, entries, mode: str, in_shift: int = 0, out_shift: int = 0,
-                 in_place: bool = False):
+                 in_place: bool = False, tls13: bool = False):
         assert mode in ("seal", "open")
         self.mode = mode
         n = len(entries)
@@ -39,11 +44,11 @@ class RecordBatch:
         in_offs, out_offs, out_lens = [], [], []
         ip = op = 0
         for i, (sid, seq, rtype, payload, kind) in enumerate(entries):
-            eiv = EXPLICIT_NONCE_LEN[kind]
+            eiv = 0 if tls13 else EXPLICIT_NONCE_LEN[kind]
             ish = in_shift[i] if isinstance(in_shift, (list, tuple)) else in_shift
             if mode == "seal":
                 ip = _align(ip, 16) + ish
-                olen = len(payload) + eiv + TAG_LEN
+                olen = len(payload) + eiv + (1 if tls13 else 0) + TAG_LEN
                 op = _align(op, 16, (16 - eiv) % 16) + out_shift
             else:
                 ip = _align(ip, 16, (16 - eiv) % 16) + ish
@@ -68,7 +73,8 @@ class RecordBatch:
             # open in place: plaintext lands at fragment + explicit nonce length
             self.d_out = self.d_in
             for i, (sid, seq, rtype, payload, kind) in enumerate(entries):
-                descs[i]["out_off"] = in_offs[i] + (EXPLICIT_NONCE_LEN[kind] if mode == "open" else 0)
+                descs[i]["out_off"] = in_offs[i] + (EXPLICIT_NONCE_LEN[kind]
+                                                    if mode == "open" and not tls13 else 0)
                 out_offs[i] = int(descs[i]["out_off"])
         else:
             self.d_out = DeviceBuffer(engine, self.out_size)

@@ -155,6 +155,11 @@ extern "C" void tlsgpu_sessions_destroy(tlsgpu_sessions* t) {
 bool tg::valid_params(const tlsgpu_session_params& p) {
   uint32_t tag = p.tag_len == 0 ? 16 : p.tag_len;
   if (tag > 16 || p.fixed_iv_len > 12) return false;
+  // TLS 1.3 (RFC 8446 section 5.3): AES-GCM only, the whole 12-byte write IV, a 16-byte tag
+  if (p.version == kTls13Version &&
+      (p.fixed_iv_len != 12 || tag != 16 ||
+       (p.aead != TLSGPU_AES_128_GCM && p.aead != TLSGPU_AES_256_GCM)))
+    return false;
   switch (p.aead) {
     case TLSGPU_AES_128_GCM: return p.key_len == 16;
     case TLSGPU_AES_256_GCM:
@@ -173,6 +178,20 @@ extern "C" int tlsgpu_sessions_install(tlsgpu_sessions* t, uint32_t first, uint3
   for (uint32_t i = 0; i < n; i++)
     if (!valid_params(params[i])) return fail(TLSGPU_EINVAL, "invalid session params at %u", i);
   if (n == 0) return TLSGPU_OK;
+  // one record generation per table (include/tlsgpu.h): the GCM kernels are
+  // compiled per generation and run_batch launches the table's set
+  {
+    std::lock_guard<std::mutex> lk(t->mu);
+    int gen = t->generation;
+    for (uint32_t i = 0; i < n; i++) {
+      const int g = params[i].version == kTls13Version ? 13 : 12;
+      if (gen != 0 && g != gen)
+        return fail(TLSGPU_EINVAL, "session %u: TLS 1.%d params in a TLS 1.%d session table", i,
+                    g - 10, gen - 10);
+      gen = g;
+    }
+    t->generation = gen;
+  }
   HIPCHK(hipSetDevice(t->eng->device));
   tlsgpu_session_params* d_params = nullptr;
   HIPCHK(hipMalloc(&d_params, sizeof(tlsgpu_session_params) * n));
@@ -385,7 +404,7 @@ static const uint32_t g_balance_snap = (uint32_t)env_uint("TLSGPU_BALANCE_SNAP",
 
 int tg::run_batch(tlsgpu_sessions* t, const void* d_descs, uint32_t n, const uint8_t* d_in,
                   uint8_t* d_out, int32_t* d_status, hipStream_t s, bool seal, bool raw,
-                  const Bounds* bounds, unsigned kinds, unsigned hints) {
+                  const Bounds* bounds, unsigned kinds, unsigned hints, tlsgpu_record* type_out) {
   if (hints == ~0u) hints = t->hints.load(std::memory_order_relaxed);
   bool have[5];
   for (int k = 0; k < 5; k++) have[k] = t->have[k] && ((kinds >> k) & 1u);
@@ -402,13 +421,22 @@ int tg::run_batch(tlsgpu_sessions* t, const void* d_descs, uint32_t n, const uin
 
   a.dbg = g_phase_stats;
   a.wg_times = wg_times_for(t->eng);
-  a.bs16_min = g_bs16_min;
+  // a TLS 1.3 table (its sessions are all TLS 1.3): the kernels compiled for
+  // that record layout, T-table record paths only (the packed bitsliced role
+  // and the experimental kernels know the TLS 1.2 layout alone)
+  const bool t13 = !raw && t->generation == 13;
+  a.tls13 = t13 ? 1u : 0u;  // the launchers forward to the TLS 1.3 kernels and the unpad pass
+  a.type_out = t13 && !seal ? type_out : nullptr;
+  a.bs16_min = t13 ? 0u : g_bs16_min;
   // batch-shape hints rule out the kernels the device would not select
   // (tlsgpu_sessions_hint); the TLSGPU_PACK / TLSGPU_PWS overrides win
   a.pack = g_pack >= 0 ? (uint32_t)g_pack : (hints & TLSGPU_HINT_NO_SHORT_RECORDS) ? 0u : 1u;
   a.pws = (g_pws == 0 && (hints & TLSGPU_HINT_SESSION_RUNS)) ? 1u : g_pws;
   int groups = groups_for(t->eng, n, &a.records_per_group);
-  const int sel_impl = g_gcm_impl.load();
+  int sel_impl = g_gcm_impl.load();
+  if (t13 && (sel_impl == TLSGPU_GCM_HYBRID || sel_impl == TLSGPU_GCM_BITSLICE ||
+                    sel_impl == TLSGPU_GCM_FUSED))
+    sel_impl = TLSGPU_GCM_QUEUE;  // the experimental kernels: TLS 1.2 tables only
   // small TLS batches (at most two records per CU): one record per workgroup,
   // its blocks split over the 16 waves, instead of one wave per record
   // (measured crossover, 16 KiB records: split 47 vs 77 us at 512 records,

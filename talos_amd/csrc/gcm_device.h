@@ -9,7 +9,25 @@
 #include "bs_aes.h"
 #include "tlsgpu_internal.h"
 
+// The TLS record layout is fixed per translation unit: TG_TLS13 = 0 (default)
+// compiles the TLS 1.2 AEAD layout (explicit nonce, 13-byte AAD), TG_TLS13 = 1
+// the TLS 1.3 one (RFC 8446 5.2-5.4) — gcm_queue13.hip, gcm_pw13.hip and
+// gcm_kernels13.hip include their TLS 1.2 twins with it set.  As runtime
+// session fields the same differences cost the queue kernel's pack variants
+// eight more spilled VGPRs, so a session table holds one
+// generation and run_batch picks the launchers (TG_GEN names) by it.
+#ifndef TG_TLS13
+#define TG_TLS13 0
+#endif
+#if TG_TLS13
+#define TG_GEN(f) f##13
+#else
+#define TG_GEN(f) f
+#endif
+
 namespace tg {
+
+constexpr bool kTls13 = TG_TLS13 != 0;
 
 static __device__ const WordTable g_te0 = kTe0;
 
@@ -625,7 +643,10 @@ struct RecCtx {
   uint32_t tag_byte;      // open: tag_in[lane] for lane < tag_len, loaded at parse
                           // time so the tag check never waits on HBM
   uint8_t* tag_out;       // seal: where the tag goes
-  uint32_t n;             // plaintext length
+  uint32_t n;             // plaintext length (TLS 1.3: the inner plaintext, content || type)
+  uint32_t inner;         // 0, or 0x100 | inner content type for a TLS 1.3 seal: src holds
+                          // n - 1 content bytes and byte n - 1 is this type (RFC 8446 5.2);
+                          // src is never read past the content
   uint32_t j0[4];         // J0 (LE words)
   uint32_t aad_be[4];     // AAD' = Horner of the AAD blocks without the final
                           // multiply (gcm128.c:826-881 folded), BE words
@@ -633,6 +654,36 @@ struct RecCtx {
   uint64_t zero_len;      // bytes of dst zero-filled on failure
   int32_t ok_status;      // status written on success
 };
+
+// Bytes of the record that come from rc.src: all of them, or all but a TLS 1.3
+// seal's synthesized type byte.  The wide full-step loops count their steps
+// over these, so the block that holds the type byte always takes a tail path
+// (load_tail) and the step loops load 16 source bytes per block as before.
+__device__ __forceinline__ uint32_t src_bytes(const RecCtx& rc) {
+  if constexpr (kTls13) return rc.n - (rc.inner >> 8);
+  return rc.n;
+}
+
+// Block i of the record's input for the tail paths, `nbytes` (0..16) of it
+// valid: load_block of the bytes that src holds, then a TLS 1.3 seal's inner
+// content type at byte n - 1.  A block that holds the type byte alone loads
+// nothing.
+template <bool SEAL>
+__device__ __forceinline__ void load_tail(const RecCtx& rc, uint32_t i, uint32_t nbytes,
+                                          bool aligned, uint32_t v[4]) {
+  if constexpr (!SEAL || !kTls13) {
+    load_block(rc.src + 16u * i, nbytes, aligned, v);
+  } else {
+    const uint32_t ns = src_bytes(rc), off = 16u * i;
+    const uint32_t lb = min(nbytes, ns > off ? ns - off : 0u);
+    load_block(rc.src + off, lb, aligned, v);
+    if (lb != nbytes) {  // the type byte is byte lb of this block
+      const uint32_t t = (rc.inner & 0xFFu) << (8u * (lb & 3u));
+#pragma unroll
+      for (uint32_t w = 0; w < 4; w++) v[w] |= (lb >> 2) == w ? t : 0u;
+    }
+  }
+}
 
 // Close the lane chains of a record: the lengths block BE64(aad bits) ||
 // BE64(ct bits) joins lane (nb % 64)'s chain at j = nb (gcm128.c:1477-1500),
@@ -683,7 +734,7 @@ __device__ __forceinline__ uint32_t gcm_close_len(const RecCtx& rc, const uint32
   return lane == 63 ? nb + 2 : 0u;  // the AAD alone (j = -1), or an empty chain
 }
 
-// This lane's share of LEN * H, LEN = BE64(13 * 8) || BE64(8 n) (BE words): lane
+// This lane's share of LEN * H, LEN = BE64(AAD bits) || BE64(8 n) (BE words): lane
 // p < kLenRows reads the entry of nibble p of the ciphertext bit count, lane
 // kLenRows an AAD entry, the others a zero entry of row 7 — one ds_read_b128 for
 // the wave; the wave sum of gcm_tag adds the shares up.  Row and nibble go
@@ -801,7 +852,7 @@ __device__ __forceinline__ void gcm_blocks(const RecCtx& rc, const DevSession* _
   // Full-block steps, two per iteration (two independent AES chains per lane
   // keep twice as many LDS lookups in flight), with the next iteration's
   // ciphertext loads issued before this iteration's AES.
-  const uint32_t nfull_steps = (n >> 4) / kWave;
+  const uint32_t nfull_steps = (src_bytes(rc) >> 4) / kWave;  // never the type byte's block
   uint32_t base = start;
   if (nfull_steps >= start / kWave + 2) {
     uint32_t c0[4], c1[4];
@@ -845,8 +896,8 @@ __device__ __forceinline__ void gcm_blocks(const RecCtx& rc, const DevSession* _
       const bool a1 = i1 < nb;
       const uint32_t nb0 = min(16u, n - 16u * i0), nb1 = a1 ? min(16u, n - 16u * i1) : 0u;
       uint32_t in0[4], in1[4], k0[4], k1[4];
-      load_block(rc.src + 16u * i0, nb0, aligned, in0);
-      load_block(rc.src + 16u * i1, nb1, aligned, in1);
+      load_tail<SEAL>(rc, i0, nb0, aligned, in0);
+      load_tail<SEAL>(rc, i1, nb1, aligned, in1);
       aes_ctr16x2<ROUNDS>(k0, k1, ctr0 + i0, ctr0 + i1, rcc, rk[3], rk, as_const(S->rk_rot), laneoff);
 #pragma unroll
       for (int w = 0; w < 4; w++) {
@@ -875,7 +926,7 @@ __device__ __forceinline__ void gcm_blocks(const RecCtx& rc, const DevSession* _
     const bool active = i < nb;
     const uint32_t nbytes = active ? min(16u, n - 16u * i) : 0u;
     uint32_t in[4];
-    load_block(rc.src + 16u * i, nbytes, aligned, in);
+    load_tail<SEAL>(rc, i, nbytes, aligned, in);
     uint32_t ks[4];
     keystream(ks, ctr0 + i);
 #pragma unroll
@@ -1078,7 +1129,7 @@ __device__ __forceinline__ void gcm_blocks_xN(const RecCtx& rc, const DevSession
   cu32* rkr = as_const(S->rk_rot);
   const uint32_t rk03 = rk[3];
   const uint32_t ctr0 = bswap32(rc.j0[3]) + 1u;
-  const uint32_t nfull_steps = (rc.n >> 4) / kWave;
+  const uint32_t nfull_steps = (src_bytes(rc) >> 4) / kWave;  // never the type byte's block
   uint32_t t = start / kWave;
   if (t + NB > nfull_steps) return;
   constexpr bool kLateGh = SEAL || !OWN;  // hash a group in the next group's rounds
@@ -1196,6 +1247,18 @@ __device__ __forceinline__ tlsgpu_record load_desc(const tlsgpu_record* p) {
 // J0 of record r for this lane (the batched constant pass): fixed IV(4) ||
 // explicit nonce(8) || 0x00000001 — the explicit nonce is the record's first
 // 8 bytes on open and the sequence number on seal (t1_enc.c:887-892, 941-948).
+// TLS 1.3 (gcm_tls13): write IV(12) XOR (0^32 || BE64(seq)) || 0x00000001, both
+// ways (RFC 8446 5.3).
+__device__ __forceinline__ bool gcm_tls13(const DevSession* __restrict__) {
+  return kTls13;  // per translation unit; the table's sessions are all of this generation
+}
+// words 1, 2 of the sequence-number nonce: seq alone (TLS 1.2 seal), or XORed
+// into the TLS 1.3 write IV
+__device__ __forceinline__ void seq_j0(const DevSession* __restrict__ S, bool t13, uint64_t seq,
+                                       uint32_t j0[4]) {
+  j0[1] = bswap32((uint32_t)(seq >> 32)) ^ (t13 ? as_const(S->fixed_nonce)[1] : 0u);
+  j0[2] = bswap32((uint32_t)seq) ^ (t13 ? as_const(S->fixed_nonce)[2] : 0u);
+}
 template <bool SEAL>
 __device__ __forceinline__ void lane_j0(const tlsgpu_record* D, uint32_t r, uint32_t run_end,
                                         const DevSession* __restrict__ S, const uint8_t* in,
@@ -1205,9 +1268,9 @@ __device__ __forceinline__ void lane_j0(const tlsgpu_record* D, uint32_t r, uint
   j0[3] = 0x01000000u;
   if (r >= run_end) return;
   const tlsgpu_record d = D[r];
-  if (SEAL) {
-    j0[1] = bswap32((uint32_t)(d.seq >> 32));
-    j0[2] = bswap32((uint32_t)d.seq);
+  const bool t13 = gcm_tls13(S);
+  if (SEAL || t13) {
+    seq_j0(S, t13, d.seq, j0);
   } else if ((d.len_type & 0xFFFFFFu) >= 8) {
     const uint8_t* p = in + d.in_off;
     j0[1] = load_u32_bytes(p);
@@ -1215,8 +1278,12 @@ __device__ __forceinline__ void lane_j0(const tlsgpu_record* D, uint32_t r, uint
   }
 }
 
-// Build the per-record context from a TLS descriptor (t1_enc.c:832-975).
-// Returns false (and writes the status) when tls1_enc would return 0.
+// Build the per-record context from a TLS descriptor (t1_enc.c:832-975; for a
+// TLS 1.3 session RFC 8446 5.2-5.3: no explicit nonce, the inner content type
+// appended on seal, the 5-byte record header as AAD).  Returns false (and
+// writes the status) when tls1_enc would return 0.  Open leaves a TLS 1.3
+// record's inner plaintext length as its status; tls13_unpad_kernel turns it
+// into the content length.
 template <bool SEAL>
 __device__ __forceinline__ bool parse_tls(const tlsgpu_record& d, const DevSession* __restrict__ S,
                                           const uint8_t* in, uint8_t* out, int32_t* status_slot,
@@ -1225,48 +1292,69 @@ __device__ __forceinline__ bool parse_tls(const tlsgpu_record& d, const DevSessi
   uint32_t type = d.len_type >> 24;
   const uint8_t* ip = in + d.in_off;
   uint8_t* op = out + d.out_off;
-  uint8_t explicit_nonce[8];
   uint32_t tag_len = as_const(&S->tag_len)[0];
-  if (SEAL ? len > TLSGPU_MAX_RECORD : (len < 8 || len - 8 < tag_len ||
-                                          len - 8 - tag_len > TLSGPU_MAX_RECORD)) {
+  const bool t13 = gcm_tls13(S);
+  const uint32_t eiv = t13 ? 0u : 8u;      // explicit nonce in the fragment
+  const uint32_t extra = t13 ? 1u : 0u;    // seal: the synthesized type byte
+  if (SEAL ? len > TLSGPU_MAX_RECORD - extra
+           : (len < eiv || len - eiv < tag_len || len - eiv - tag_len > TLSGPU_MAX_RECORD)) {
     if (lane == 0) *status_slot = TLSGPU_REC_PUBLIC_INVALID;
     return false;
   }
+  uint32_t e1, e2;  // nonce words 1, 2
   if (SEAL) {
-    rc.n = len;
+    rc.n = len + extra;
+    rc.inner = t13 ? 0x100u | type : 0u;
     rc.src = ip;
-    rc.dst = op + 8;
-    rc.tag_out = op + 8 + len;
+    rc.dst = op + eiv;
+    rc.tag_out = op + eiv + rc.n;
     rc.tag_in = nullptr;
-    for (int k = 0; k < 8; k++) explicit_nonce[k] = (uint8_t)(d.seq >> (56 - 8 * k));
-    if (lane < 8) op[lane] = (uint8_t)(d.seq >> (56 - 8 * lane));  // explicit nonce into the record
-    rc.ok_status = (int32_t)(len + 8 + tag_len);
+    if (lane < eiv) op[lane] = (uint8_t)(d.seq >> (56 - 8 * lane));  // explicit nonce into the record
+    rc.ok_status = (int32_t)(rc.n + eiv + tag_len);
     rc.zero_len = 0;
   } else {
-    for (int k = 0; k < 8; k++) explicit_nonce[k] = ip[k];
-    rc.n = len - 8 - tag_len;
-    rc.src = ip + 8;
+    rc.n = len - eiv - tag_len;
+    rc.inner = 0;
+    rc.src = ip + eiv;
     rc.dst = op;
-    rc.tag_in = ip + 8 + rc.n;
+    rc.tag_in = ip + eiv + rc.n;
     rc.tag_byte = lane < tag_len ? rc.tag_in[lane] : 0u;
     rc.tag_out = nullptr;
     rc.ok_status = (int32_t)rc.n;
     rc.zero_len = rc.n;
   }
-  // nonce = fixed_iv(4) || explicit(8); J0 = nonce || 0x00000001
+  // TLS 1.2: nonce = fixed_iv(4) || explicit(8), the explicit nonce being the
+  // sequence number (seal) or the fragment's first 8 bytes (open); TLS 1.3:
+  // the write IV with the sequence number XORed in.  J0 = nonce || 0x00000001
+  uint32_t sj[4];
+  seq_j0(S, t13, d.seq, sj);
+  if (SEAL || t13) {
+    e1 = sj[1];
+    e2 = sj[2];
+  } else {
+    e1 = (uint32_t)ip[0] | ((uint32_t)ip[1] << 8) | ((uint32_t)ip[2] << 16) | ((uint32_t)ip[3] << 24);
+    e2 = (uint32_t)ip[4] | ((uint32_t)ip[5] << 8) | ((uint32_t)ip[6] << 16) | ((uint32_t)ip[7] << 24);
+  }
   rc.j0[0] = as_const(S->fixed_nonce)[0];
-  rc.j0[1] = (uint32_t)explicit_nonce[0] | ((uint32_t)explicit_nonce[1] << 8) |
-             ((uint32_t)explicit_nonce[2] << 16) | ((uint32_t)explicit_nonce[3] << 24);
-  rc.j0[2] = (uint32_t)explicit_nonce[4] | ((uint32_t)explicit_nonce[5] << 8) |
-             ((uint32_t)explicit_nonce[6] << 16) | ((uint32_t)explicit_nonce[7] << 24);
+  rc.j0[1] = e1;
+  rc.j0[2] = e2;
   rc.j0[3] = 0x01000000u;
-  // AAD = seq(8) || type || version(2) || length(2), one zero-padded block
-  uint32_t v = as_const(&S->version)[0];
-  rc.aad_be[0] = (uint32_t)(d.seq >> 32);
-  rc.aad_be[1] = (uint32_t)d.seq;
-  rc.aad_be[2] = (type << 24) | ((v & 0xFFFF) << 8) | ((rc.n >> 8) & 0xFF);
-  rc.aad_be[3] = (rc.n & 0xFF) << 24;
-  rc.aad_len = 13;
+  if (t13) {
+    // AAD = 0x17 0x03 0x03 BE16(ciphertext length with the tag), one zero-padded block
+    const uint32_t cl = rc.n + tag_len;
+    rc.aad_be[0] = 0x17030300u | ((cl >> 8) & 0xFF);
+    rc.aad_be[1] = (cl & 0xFF) << 24;
+    rc.aad_be[2] = rc.aad_be[3] = 0;
+    rc.aad_len = 5;
+  } else {
+    // AAD = seq(8) || type || version(2) || length(2), one zero-padded block
+    uint32_t v = as_const(&S->version)[0];
+    rc.aad_be[0] = (uint32_t)(d.seq >> 32);
+    rc.aad_be[1] = (uint32_t)d.seq;
+    rc.aad_be[2] = (type << 24) | ((v & 0xFFFF) << 8) | ((rc.n >> 8) & 0xFF);
+    rc.aad_be[3] = (rc.n & 0xFF) << 24;
+    rc.aad_len = 13;
+  }
   return true;
 }
 
@@ -1279,6 +1367,7 @@ __device__ __forceinline__ void parse_raw(const RawJob& j, const DevSession* __r
   uint8_t* op = (uint8_t*)j.out;
   const uint8_t* nonce = (const uint8_t*)j.nonce;
   uint32_t tag_len = as_const(&S->tag_len)[0];
+  rc.inner = 0;
   if (SEAL) {
     rc.n = j.in_len;
     rc.src = ip;
@@ -1404,8 +1493,9 @@ __device__ void load_session_tables(const DevGcmTables* __restrict__ tab) {
 
 // The session's lengths-block table (LEN_OFF, read by len_term), BE words:
 // entry 16 p + v is (nibble v at nibble p of the ciphertext bit count) * H for
-// p < kLenRows, BE64(13 * 8) * H (the TLS AAD of parse_tls) for p = kLenRows,
-// zero for p = 7.  With T[v] the H^1 Shoup entries and s() the 4-bit shift of
+// p < kLenRows, BE64(ab) * H for p = kLenRows (ab = the AAD bits of parse_tls:
+// 13 * 8 for TLS 1.2, 5 * 8 for TLS 1.3), zero for p = 7.  With T[v] the H^1
+// Shoup entries and s() the 4-bit shift of
 // mul_shoup, X * H is the Horner sum z = s(z) ^ T[nibble k] over X's nibbles
 // k = 0..31 (k = 0: the low nibble of byte 15), so a nibble v alone at k gives
 // s^(31 - k)(T[v]).  Reads the table in global memory, so it needs no barrier
@@ -1413,7 +1503,7 @@ __device__ void load_session_tables(const DevGcmTables* __restrict__ tab) {
 // have two entries of that copy each).
 template <int NT>
 __device__ void load_len_table(const DevGcmTables* __restrict__ tab) {
-  constexpr uint32_t ab = 13 * 8;  // AAD bits: nibble k = 16 is ab & 15, k = 17 is ab >> 4
+  constexpr uint32_t ab = kTls13 ? 5 * 8 : 13 * 8;  // AAD bits: nibble k = 16 is ab & 15, k = 17 is ab >> 4
   static_assert(ab < 256, "two nibbles");
   static_assert(NT >= (int)kLenEntries, "one entry per thread");
   const uint4* sh = reinterpret_cast<const uint4*>(&tab->shoup[0][0][0]);

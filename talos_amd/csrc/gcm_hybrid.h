@@ -306,8 +306,11 @@ namespace tg {
 __device__ __forceinline__ bool rec_in_bounds(const tlsgpu_record& d, const DevSession* S,
                                               uint64_t in_bytes, uint64_t out_bytes, bool seal) {
   const uint64_t eiv = as_const(&S->nonce_in_record)[0] ? 8u : 0u, tag = as_const(&S->tag_len)[0];
+  // a TLS 1.3 seal writes content || type || tag
+  uint64_t extra = 0;
+  if constexpr (kTls13) extra = is_gcm(as_const(&S->kind)[0]) ? 1u : 0u;
   const uint64_t len = d.len_type & 0xFFFFFFu;
-  const uint64_t out_len = seal ? len + eiv + tag : (len >= eiv + tag ? len - eiv - tag : 0);
+  const uint64_t out_len = seal ? len + eiv + extra + tag : (len >= eiv + tag ? len - eiv - tag : 0);
   return !(d.in_off > in_bytes || len > in_bytes - d.in_off || d.out_off > out_bytes ||
            out_len > out_bytes - d.out_off);
 }
@@ -412,11 +415,13 @@ constexpr uint32_t kPackNone = 0xFFu;
 
 // Lanes record descriptor word len_type needs in a pack, or kPackNone when it
 // takes the single-record path (too long, or publicly invalid: parse_tls).
+// eiv: the session's explicit nonce length, 8 (TLS 1.2) or 0 (TLS 1.3, whose
+// seal also appends the type byte): nb counts blocks of inner plaintext.
 template <bool SEAL>
-__device__ __forceinline__ uint32_t pack_need(uint32_t len_type, uint32_t tag_len) {
+__device__ __forceinline__ uint32_t pack_need(uint32_t len_type, uint32_t tag_len, uint32_t eiv) {
   const uint32_t len = len_type & 0xFFFFFFu;
-  if (!SEAL && len < 8 + tag_len) return kPackNone;
-  const uint32_t n = SEAL ? len : len - 8 - tag_len;
+  if (!SEAL && len < eiv + tag_len) return kPackNone;
+  const uint32_t n = SEAL ? len + (eiv ? 0u : 1u) : len - eiv - tag_len;
   const uint32_t nb = (n + 15) >> 4;
   return nb + 2 <= kPackMaxNeed ? nb + 2 : kPackNone;
 }
@@ -433,6 +438,8 @@ __device__ void gcm_pack(const BatchArgs& a, const RecPre* __restrict__ pre, uin
   cu32* rkr = as_const(S->rk_rot);
   const uint32_t tag_len = as_const(&S->tag_len)[0];
   const uint32_t version = as_const(&S->version)[0];
+  const bool t13 = gcm_tls13(S);
+  const uint32_t eiv = t13 ? 0u : 8u;
   // lane layout: exclusive prefix sum of the needs
   const uint32_t own = lane < k ? need : 0u;
 #ifndef TG_PACK_SHFL_SCAN
@@ -460,9 +467,9 @@ __device__ void gcm_pack(const BatchArgs& a, const RecPre* __restrict__ pre, uin
   const uint32_t len = d.len_type & 0xFFFFFFu;
   const uint8_t* ip = a.in + d.in_off;
   uint8_t* op = a.out + d.out_off;
-  const uint32_t n = SEAL ? len : len - 8 - tag_len;
-  const uint8_t* src = SEAL ? ip : ip + 8;
-  uint8_t* dst = SEAL ? op + 8 : op;
+  const uint32_t n = SEAL ? len + (t13 ? 1u : 0u) : len - eiv - tag_len;
+  const uint8_t* src = SEAL ? ip : ip + eiv;
+  uint8_t* dst = SEAL ? op + eiv : op;
   const uint4* P = reinterpret_cast<const uint4*>(pre + r);
   const uint4 p0 = P[0], p1 = P[1], p2 = P[2];
   RecConsts rcc;
@@ -476,7 +483,15 @@ __device__ void gcm_pack(const BatchArgs& a, const RecPre* __restrict__ pre, uin
   const uint32_t nbytes = blk ? min(16u, n - 16u * jb) : 0u;
   const bool aligned = ((((uintptr_t)(src + 16u * jb)) | ((uintptr_t)(dst + 16u * jb))) & 15) == 0;
   uint32_t in[4] = {0, 0, 0, 0}, ks[4];
-  if (blk) load_block(src + 16u * jb, nbytes, aligned, in);
+  // a TLS 1.3 seal: the last block's last byte is the inner content type, not
+  // read from src (load_tail, gcm_device.h)
+  const uint32_t lbytes = SEAL && t13 ? min(nbytes, len - min(len, 16u * jb)) : nbytes;
+  if (blk) load_block(src + 16u * jb, lbytes, aligned, in);
+  if (SEAL && lbytes != nbytes) {
+    const uint32_t t = (d.len_type >> 24) << (8u * (lbytes & 3u));
+#pragma unroll
+    for (uint32_t w = 0; w < 4; w++) in[w] |= (lbytes >> 2) == w ? t : 0u;
+  }
   uint32_t tagw[4] = {0, 0, 0, 0};  // open: received tag (lengths lane)
   const bool last = used && j == (int32_t)nb;
   if (!SEAL && last) {
@@ -498,20 +513,24 @@ __device__ void gcm_pack(const BatchArgs& a, const RecPre* __restrict__ pre, uin
   if (blk) {
     const uint32_t* c = SEAL ? ob : in;
     e[0] = bswap32(c[0]); e[1] = bswap32(c[1]); e[2] = bswap32(c[2]); e[3] = bswap32(c[3]);
+  } else if (j == -1 && t13) {  // AAD = 0x17 0x03 0x03 BE16(n + tag) (RFC 8446 5.2)
+    e[0] = 0x17030300u | (((n + tag_len) >> 8) & 0xFF);
+    e[1] = ((n + tag_len) & 0xFF) << 24;
+    e[2] = e[3] = 0;
   } else if (j == -1) {  // AAD = seq || type || version || length (t1_enc.c:841-847,961-962)
     e[0] = (uint32_t)(d.seq >> 32);
     e[1] = (uint32_t)d.seq;
     e[2] = ((d.len_type >> 24) << 24) | ((version & 0xFFFF) << 8) | ((n >> 8) & 0xFF);
     e[3] = (n & 0xFF) << 24;
-  } else {  // lengths block: BE64(13 * 8) || BE64(n * 8)
-    e[0] = 0; e[1] = 13u * 8u;
+  } else {  // lengths block: BE64(AAD bits) || BE64(n * 8)
+    e[0] = 0; e[1] = t13 ? 5u * 8u : 13u * 8u;
     e[2] = (uint32_t)(((uint64_t)n * 8) >> 32); e[3] = (uint32_t)((uint64_t)n * 8);
   }
   // open stores its plaintext now too and overwrites it with zeros below when
   // the record's tag fails (as gcm_record's zero_len fill): ob is not held
   // live through the multiply
   if (blk) store_block(dst + 16u * jb, nbytes, aligned, ob);
-  if (SEAL && used && j == -1) {
+  if (SEAL && used && j == -1 && !t13) {
     for (int b = 0; b < 8; b++) op[b] = (uint8_t)(d.seq >> (56 - 8 * b));  // explicit nonce
   }
   // y = E_j * H^(nb + 1 - j), then the per-record XOR: inclusive scan, minus
@@ -549,7 +568,7 @@ __device__ void gcm_pack(const BatchArgs& a, const RecPre* __restrict__ pre, uin
       } else {
         for (uint32_t b = 0; b < tag_len; b++) to[b] = (uint8_t)(tag[b >> 2] >> (8 * (b & 3)));
       }
-      *slot = (int32_t)(len + 8 + tag_len);
+      *slot = (int32_t)(n + eiv + tag_len);
     } else {
       uint32_t diff = 0;
 #pragma unroll
@@ -678,9 +697,11 @@ __device__ void fused_prologue_map(const BatchArgs& a, RecPre* __restrict__ pre,
     j0[0] = *reinterpret_cast<const uint32_t*>(S->fixed_nonce);
     j0[1] = j0[2] = 0;
     j0[3] = 0x01000000u;
-    if (SEAL) {
-      j0[1] = bswap32((uint32_t)(d.seq >> 32));
-      j0[2] = bswap32((uint32_t)d.seq);
+    constexpr bool t13 = kTls13;  // TLS 1.3: the write IV XOR the sequence number
+    if (SEAL || t13) {
+      const uint32_t* fx = reinterpret_cast<const uint32_t*>(S->fixed_nonce);
+      j0[1] = bswap32((uint32_t)(d.seq >> 32)) ^ (t13 ? fx[1] : 0u);
+      j0[2] = bswap32((uint32_t)d.seq) ^ (t13 ? fx[2] : 0u);
     } else if ((d.len_type & 0xFFFFFFu) >= 8) {
       const uint8_t* p = a.in + d.in_off;
       j0[1] = load_u32_bytes(p);
@@ -804,8 +825,10 @@ __device__ uint32_t work_cut(const BatchArgs& a, uint32_t k) {
 // 16 waves of <= 128 VGPRs), T-table waves NB blocks wide; B16W > 0: the first
 // B16W waves take the packed bitsliced role (hy_b16_record, one per SIMD for
 // B16W = 4: waves go to the SIMDs in turn).
+// TG_GEN: gcm_hy_kernel13 in a TLS 1.3 translation unit (both generations'
+// instantiations live in one library; the TLS 1.2 kernels keep their names).
 template <bool SEAL, int ROUNDS, int NT, int BSW, int NB, bool PACK = false, int B16W = 0>
-__global__ __launch_bounds__(NT, 1) void gcm_hy_kernel(BatchArgs a,
+__global__ __launch_bounds__(NT, 1) void TG_GEN(gcm_hy_kernel)(BatchArgs a,
                                                        const RecPre* __restrict__ pre) {
   // pack and no-pack variants are separate kernels (the pack code costs the
   // long-record loop SGPR spills), and the per-wave-session kernel replaces both
@@ -942,8 +965,9 @@ __global__ __launch_bounds__(NT, 1) void gcm_hy_kernel(BatchArgs a,
     const bool in_range = sid < a.n_sessions;
     const DevSession* __restrict__ S = a.sessions + (in_range ? sid : 0);
     const uint32_t tag_len = as_const(&S->tag_len)[0];
+    constexpr uint32_t eiv = kTls13 ? 0u : 8u;
     const uint32_t run_cap = packing ? min(rhi, pos + kPlanCap) : rhi;
-    bool has_short = packing && pack_need<SEAL>(as_const(&D[pos].len_type)[0], tag_len) <= kPackMaxNeed;
+    bool has_short = packing && pack_need<SEAL>(as_const(&D[pos].len_type)[0], tag_len, eiv) <= kPackMaxNeed;
     uint32_t run_end = pos + 1;
     // the run's end: 4 x 64 descriptors per memory round trip (the scan is
     // on the run-to-run critical path of the wave that finished last; round 5,
@@ -963,7 +987,7 @@ __global__ __launch_bounds__(NT, 1) void gcm_hy_kernel(BatchArgs a,
         const uint32_t p = run_end + 64u * u + lane;
         if (packing)  // a hint only: records past the run's end may count
           has_short |= __ballot(p < run_cap && s[u] == sid &&
-                                pack_need<SEAL>(lt[u], tag_len) <= kPackMaxNeed) != 0;
+                                pack_need<SEAL>(lt[u], tag_len, eiv) <= kPackMaxNeed) != 0;
         const uint64_t diff = __ballot(p < run_cap && s[u] != sid);
         if (diff && found == 0xFFFFFFFFu)
           found = 64u * u + __builtin_amdgcn_readfirstlane((uint32_t)__builtin_ctzll(diff));
@@ -989,7 +1013,7 @@ __global__ __launch_bounds__(NT, 1) void gcm_hy_kernel(BatchArgs a,
         __syncthreads();
         for (uint32_t c = wave * kWave; c < run_len; c += NT) {  // ballot compaction per wave
           const uint32_t t = c + lane;
-          const uint32_t nd = t < run_len ? pack_need<SEAL>(D[pos + t].len_type, tag_len) : 0u;
+          const uint32_t nd = t < run_len ? pack_need<SEAL>(D[pos + t].len_type, tag_len, eiv) : 0u;
           // fused: an out-of-bounds record takes the long-record path, which
           // skips it (its status was written by the prologue)
           const bool sh = t < run_len && nd <= kPackMaxNeed &&
@@ -1141,7 +1165,7 @@ __global__ __launch_bounds__(NT, 1) void gcm_hy_kernel(BatchArgs a,
 // belong to one session (the common case: sessions form runs), else per lane.
 constexpr int kPrepThreads = 512;
 template <bool SEAL, int ROUNDS>
-__global__ __launch_bounds__(kPrepThreads) void gcm_prep_kernel(BatchArgs a,
+__global__ __launch_bounds__(kPrepThreads) void TG_GEN(gcm_prep_kernel)(BatchArgs a,
                                                                 RecPre* __restrict__ pre) {
   __shared__ uint32_t te[256 * 32];
   __shared__ uint32_t cnt[3];  // packable flag, run starts, records of this key size
@@ -1163,7 +1187,8 @@ __global__ __launch_bounds__(kPrepThreads) void gcm_prep_kernel(BatchArgs a,
       S = a.sessions + d.session;
       mine = is_gcm(S->kind) && (int)S->rounds == ROUNDS;
       run_start = mine && (r == 0 || D[r - 1].session != d.session);
-      packable = mine && pack_need<SEAL>(d.len_type, S->tag_len) <= kPackMaxNeed;
+      packable = mine && pack_need<SEAL>(d.len_type, S->tag_len, kTls13 ? 0u : 8u) <=
+                             kPackMaxNeed;
     }
   }
   // selection words (a.sel, SelSums): summed per wave (ballot), per workgroup
@@ -1195,9 +1220,11 @@ __global__ __launch_bounds__(kPrepThreads) void gcm_prep_kernel(BatchArgs a,
   j0[0] = *reinterpret_cast<const uint32_t*>(S->fixed_nonce);
   j0[1] = j0[2] = 0;
   j0[3] = 0x01000000u;
-  if (SEAL) {
-    j0[1] = bswap32((uint32_t)(d.seq >> 32));
-    j0[2] = bswap32((uint32_t)d.seq);
+  constexpr bool t13 = kTls13;  // TLS 1.3: the write IV XOR the sequence number
+  if (SEAL || t13) {
+    const uint32_t* fx = reinterpret_cast<const uint32_t*>(S->fixed_nonce);
+    j0[1] = bswap32((uint32_t)(d.seq >> 32)) ^ (t13 ? fx[1] : 0u);
+    j0[2] = bswap32((uint32_t)d.seq) ^ (t13 ? fx[2] : 0u);
   } else if ((d.len_type & 0xFFFFFFu) >= 8) {
     const uint8_t* p = a.in + d.in_off;
     j0[1] = load_u32_bytes(p);

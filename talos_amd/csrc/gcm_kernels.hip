@@ -30,8 +30,11 @@
 
 namespace tg {
 
+// TG_GEN (here and for gcm_raw_kernel): gcm_batch_kernel13 when gcm_kernels13.hip
+// compiles this file again with TG_TLS13 (gcm_device.h), for the TLS batch
+// kernels alone.
 template <bool SEAL, bool RAW, int ROUNDS>
-__global__ __launch_bounds__(kThreads, 1) void gcm_batch_kernel(BatchArgs a) {
+__global__ __launch_bounds__(kThreads, 1) void TG_GEN(gcm_batch_kernel)(BatchArgs a) {
   const uint32_t lane = threadIdx.x & 63;
   const uint32_t wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   const uint32_t laneoff = aes_laneoff(lane);
@@ -109,38 +112,57 @@ __global__ __launch_bounds__(kThreads, 1) void gcm_batch_kernel(BatchArgs a) {
 
 // Raw EVP jobs and small TLS batches: one job per workgroup (gcm_raw.h).
 template <bool SEAL, int ROUNDS, bool TLS = false>
-__global__ __launch_bounds__(kThreads, 1) void gcm_raw_kernel(BatchArgs a) {
+__global__ __launch_bounds__(kThreads, 1) void TG_GEN(gcm_raw_kernel)(BatchArgs a) {
   fill_aes_lds<kThreads>();  // the job's barrier after its table load covers this
   gcm_raw_job<SEAL, ROUNDS, TLS>(a, blockIdx.x);
 }
 
 template <bool SEAL, int ROUNDS, bool TLS = false>
 static int launch_raw(const BatchArgs& a, hipStream_t s) {
-  hipLaunchKernelGGL((gcm_raw_kernel<SEAL, ROUNDS, TLS>), dim3(a.n), dim3(kThreads), 0, s, a);
+  hipLaunchKernelGGL((TG_GEN(gcm_raw_kernel)<SEAL, ROUNDS, TLS>), dim3(a.n), dim3(kThreads), 0, s, a);
   return hipGetLastError() == hipSuccess ? 0 : -1;
 }
 
-int launch_gcm_split(const BatchArgs& a, bool seal, int rounds, hipStream_t s) {
+int TG_GEN(launch_gcm_split)(const BatchArgs& a, bool seal, int rounds, hipStream_t s) {
   if (a.n == 0) return 0;
-  if (rounds == 10) return seal ? launch_raw<true, 10, true>(a, s) : launch_raw<false, 10, true>(a, s);
-  return seal ? launch_raw<true, 14, true>(a, s) : launch_raw<false, 14, true>(a, s);
+#if !TG_TLS13
+  if (a.tls13) return launch_gcm_split13(a, seal, rounds, s);  // a TLS 1.3 table
+#endif
+  const int rc = rounds == 10
+                     ? (seal ? launch_raw<true, 10, true>(a, s) : launch_raw<false, 10, true>(a, s))
+                     : (seal ? launch_raw<true, 14, true>(a, s) : launch_raw<false, 14, true>(a, s));
+#if TG_TLS13
+  if (rc == 0 && !seal) return launch_tls13_unpad(a, rounds, s);  // open: content lengths
+#endif
+  return rc;
 }
 
 template <bool SEAL, bool RAW, int ROUNDS>
 static int launch_one(const BatchArgs& a, int groups, hipStream_t s) {
-  hipLaunchKernelGGL((gcm_batch_kernel<SEAL, RAW, ROUNDS>), dim3(groups), dim3(kThreads), 0, s, a);
+  hipLaunchKernelGGL((TG_GEN(gcm_batch_kernel)<SEAL, RAW, ROUNDS>), dim3(groups), dim3(kThreads), 0, s, a);
   return hipGetLastError() == hipSuccess ? 0 : -1;
 }
 
-int launch_gcm(const BatchArgs& a, bool seal, bool raw, int rounds, int groups, hipStream_t s) {
+int TG_GEN(launch_gcm)(const BatchArgs& a, bool seal, bool raw, int rounds, int groups,
+                       hipStream_t s) {
   if (a.n == 0) return 0;
+#if TG_TLS13
+  if (raw) return -1;  // raw EVP jobs carry their own nonce and AAD: the TLS 1.2 unit's kernels
+#else
   if (raw) {  // one workgroup per job (a.n jobs), blocks split over its waves
     if (rounds == 10) return seal ? launch_raw<true, 10>(a, s) : launch_raw<false, 10>(a, s);
     return seal ? launch_raw<true, 14>(a, s) : launch_raw<false, 14>(a, s);
   }
-  if (rounds == 10)
-    return seal ? launch_one<true, false, 10>(a, groups, s) : launch_one<false, false, 10>(a, groups, s);
-  return seal ? launch_one<true, false, 14>(a, groups, s) : launch_one<false, false, 14>(a, groups, s);
+  if (a.tls13) return launch_gcm13(a, seal, raw, rounds, groups, s);  // a TLS 1.3 table
+#endif
+  const int rc =
+      rounds == 10
+          ? (seal ? launch_one<true, false, 10>(a, groups, s) : launch_one<false, false, 10>(a, groups, s))
+          : (seal ? launch_one<true, false, 14>(a, groups, s) : launch_one<false, false, 14>(a, groups, s));
+#if TG_TLS13
+  if (rc == 0 && !seal) return launch_tls13_unpad(a, rounds, s);  // open: content lengths
+#endif
+  return rc;
 }
 
 }  // namespace tg

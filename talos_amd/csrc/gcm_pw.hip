@@ -224,8 +224,10 @@ __device__ __forceinline__ GhNib gh_nib(uint32_t lane, uint32_t base) {
   return g;
 }
 
+// TG_GEN: gcm_pw_kernel13 when gcm_pw13.hip compiles this file again with
+// TG_TLS13 (gcm_device.h)
 template <bool SEAL, int ROUNDS>
-__global__ __launch_bounds__(kPwThreads, 1) void gcm_pw_kernel(BatchArgs a,
+__global__ __launch_bounds__(kPwThreads, 1) void TG_GEN(gcm_pw_kernel)(BatchArgs a,
                                                                const RecPre* __restrict__ pre) {
   const SelSums f = sel_sums(a.sel);
   if (!pws_selected(a.pws, f.runs, f.recs)) return;  // the queue kernel runs this batch
@@ -266,16 +268,16 @@ __global__ __launch_bounds__(kPwThreads, 1) void gcm_pw_kernel(BatchArgs a,
   }
 }
 
-int launch_gcm_pw(const BatchArgs& a, const RecPre* pre, bool seal, int rounds, int groups,
-                  hipStream_t s) {
+int TG_GEN(launch_gcm_pw)(const BatchArgs& a, const RecPre* pre, bool seal, int rounds, int groups,
+                           hipStream_t s) {
   if (a.n == 0 || !a.sel || !a.wg_next) return 0;
   const dim3 g(groups), b(kPwThreads);
   if (rounds == 10) {
-    if (seal) hipLaunchKernelGGL((gcm_pw_kernel<true, 10>), g, b, 0, s, a, pre);
-    else hipLaunchKernelGGL((gcm_pw_kernel<false, 10>), g, b, 0, s, a, pre);
+    if (seal) hipLaunchKernelGGL((TG_GEN(gcm_pw_kernel)<true, 10>), g, b, 0, s, a, pre);
+    else hipLaunchKernelGGL((TG_GEN(gcm_pw_kernel)<false, 10>), g, b, 0, s, a, pre);
   } else {
-    if (seal) hipLaunchKernelGGL((gcm_pw_kernel<true, 14>), g, b, 0, s, a, pre);
-    else hipLaunchKernelGGL((gcm_pw_kernel<false, 14>), g, b, 0, s, a, pre);
+    if (seal) hipLaunchKernelGGL((TG_GEN(gcm_pw_kernel)<true, 14>), g, b, 0, s, a, pre);
+    else hipLaunchKernelGGL((TG_GEN(gcm_pw_kernel)<false, 14>), g, b, 0, s, a, pre);
   }
   return hipGetLastError() == hipSuccess ? 0 : -1;
 }

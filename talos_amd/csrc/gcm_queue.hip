@@ -1,6 +1,9 @@
 // gcm_queue.hip — the per-record prep pass and the T-table queue kernel
 // (gcm_hy_kernel<1024 threads, no bitsliced waves, 2 blocks per lane>), the
-// default AES-GCM TLS batch path.
+// default AES-GCM TLS batch path.  gcm_queue13.hip
+// compiles this file again for the TLS 1.3 record layout (TG_TLS13, gcm_device.h):
+// the launchers then carry the suffix 13 (TG_GEN) and the batch-plan kernels,
+// which read descriptors only, stay those of this unit.
 #include "gcm_hybrid.h"
 
 namespace tg {
@@ -9,19 +12,23 @@ namespace tg {
 #define TG_QUEUE_NB 2
 #endif
 
-int launch_gcm_prep(const BatchArgs& a, RecPre* pre, bool seal, int rounds, hipStream_t s) {
+int TG_GEN(launch_gcm_prep)(const BatchArgs& a, RecPre* pre, bool seal, int rounds, hipStream_t s) {
   if (a.n == 0) return 0;
+#if !TG_TLS13
+  if (a.tls13) return launch_gcm_prep13(a, pre, seal, rounds, s);  // a TLS 1.3 table
+#endif
   const dim3 g((a.n + kPrepThreads - 1) / kPrepThreads), b(kPrepThreads);
   if (rounds == 10) {
-    if (seal) hipLaunchKernelGGL((gcm_prep_kernel<true, 10>), g, b, 0, s, a, pre);
-    else hipLaunchKernelGGL((gcm_prep_kernel<false, 10>), g, b, 0, s, a, pre);
+    if (seal) hipLaunchKernelGGL((TG_GEN(gcm_prep_kernel)<true, 10>), g, b, 0, s, a, pre);
+    else hipLaunchKernelGGL((TG_GEN(gcm_prep_kernel)<false, 10>), g, b, 0, s, a, pre);
   } else {
-    if (seal) hipLaunchKernelGGL((gcm_prep_kernel<true, 14>), g, b, 0, s, a, pre);
-    else hipLaunchKernelGGL((gcm_prep_kernel<false, 14>), g, b, 0, s, a, pre);
+    if (seal) hipLaunchKernelGGL((TG_GEN(gcm_prep_kernel)<true, 14>), g, b, 0, s, a, pre);
+    else hipLaunchKernelGGL((TG_GEN(gcm_prep_kernel)<false, 14>), g, b, 0, s, a, pre);
   }
   return hipGetLastError() == hipSuccess ? 0 : -1;
 }
 
+#if !TG_TLS13
 // Work-balanced ranges (round 5, engine.cpp run_batch): the work
 // (cut_work_of) of each count range [g * rpg, (g + 1) * rpg), one workgroup
 // per range; the queue kernel's prologue cuts the batch at equal work from
@@ -175,12 +182,16 @@ int launch_piece_plan(const BatchArgs& a, int groups, uint8_t* scratch, const ui
   *n_pieces = np;
   return hipGetLastError() == hipSuccess ? 0 : -1;
 }
+#endif  // !TG_TLS13
 
-int launch_gcm_queue(const BatchArgs& a, const RecPre* pre, bool seal, int rounds, int groups,
-                     hipStream_t s) {
+int TG_GEN(launch_gcm_queue)(const BatchArgs& a, const RecPre* pre, bool seal, int rounds,
+                              int groups, hipStream_t s) {
   if (a.n == 0) return 0;
+#if !TG_TLS13
+  if (a.tls13) return launch_gcm_queue13(a, pre, seal, rounds, groups, s);  // a TLS 1.3 table
+#endif
   const dim3 g(groups), b(1024);
-#ifdef TG_EXPERIMENTAL
+#if defined(TG_EXPERIMENTAL) && !TG_TLS13
   if (a.bs16_min != 0 && a.sel) {  // no-pack variant with bitsliced waves (gcm_queue_b16.hip)
     if (launch_gcm_queue_b16(a, pre, seal, rounds, groups, s)) return -1;
   } else
@@ -188,23 +199,28 @@ int launch_gcm_queue(const BatchArgs& a, const RecPre* pre, bool seal, int round
   if (a.fused && a.pack) {
     // fused (engine.cpp run_batch): only the pack variant runs, with its own prologue
   } else if (rounds == 10) {
-    if (seal) hipLaunchKernelGGL((gcm_hy_kernel<true, 10, 1024, 0, TG_QUEUE_NB>), g, b, 0, s, a, pre);
-    else hipLaunchKernelGGL((gcm_hy_kernel<false, 10, 1024, 0, TG_QUEUE_NB>), g, b, 0, s, a, pre);
+    if (seal) hipLaunchKernelGGL((TG_GEN(gcm_hy_kernel)<true, 10, 1024, 0, TG_QUEUE_NB>), g, b, 0, s, a, pre);
+    else hipLaunchKernelGGL((TG_GEN(gcm_hy_kernel)<false, 10, 1024, 0, TG_QUEUE_NB>), g, b, 0, s, a, pre);
   } else {
-    if (seal) hipLaunchKernelGGL((gcm_hy_kernel<true, 14, 1024, 0, TG_QUEUE_NB>), g, b, 0, s, a, pre);
-    else hipLaunchKernelGGL((gcm_hy_kernel<false, 14, 1024, 0, TG_QUEUE_NB>), g, b, 0, s, a, pre);
+    if (seal) hipLaunchKernelGGL((TG_GEN(gcm_hy_kernel)<true, 14, 1024, 0, TG_QUEUE_NB>), g, b, 0, s, a, pre);
+    else hipLaunchKernelGGL((TG_GEN(gcm_hy_kernel)<false, 14, 1024, 0, TG_QUEUE_NB>), g, b, 0, s, a, pre);
   }
   if ((a.sel || a.fused) && a.pack) {  // the pack variant: runs instead when the prep pass saw a short record
     if (rounds == 10) {
-      if (seal) hipLaunchKernelGGL((gcm_hy_kernel<true, 10, 1024, 0, TG_QUEUE_NB, true>), g, b, 0, s, a, pre);
-      else hipLaunchKernelGGL((gcm_hy_kernel<false, 10, 1024, 0, TG_QUEUE_NB, true>), g, b, 0, s, a, pre);
+      if (seal) hipLaunchKernelGGL((TG_GEN(gcm_hy_kernel)<true, 10, 1024, 0, TG_QUEUE_NB, true>), g, b, 0, s, a, pre);
+      else hipLaunchKernelGGL((TG_GEN(gcm_hy_kernel)<false, 10, 1024, 0, TG_QUEUE_NB, true>), g, b, 0, s, a, pre);
     } else {
-      if (seal) hipLaunchKernelGGL((gcm_hy_kernel<true, 14, 1024, 0, TG_QUEUE_NB, true>), g, b, 0, s, a, pre);
-      else hipLaunchKernelGGL((gcm_hy_kernel<false, 14, 1024, 0, TG_QUEUE_NB, true>), g, b, 0, s, a, pre);
+      if (seal) hipLaunchKernelGGL((TG_GEN(gcm_hy_kernel)<true, 14, 1024, 0, TG_QUEUE_NB, true>), g, b, 0, s, a, pre);
+      else hipLaunchKernelGGL((TG_GEN(gcm_hy_kernel)<false, 14, 1024, 0, TG_QUEUE_NB, true>), g, b, 0, s, a, pre);
     }
   }
-  if (a.sel && a.pws != 1 && hipGetLastError() == hipSuccess)  // per-wave sessions (gcm_pw.hip)
-    return launch_gcm_pw(a, pre, seal, rounds, groups, s);
+  if (a.sel && a.pws != 1 && hipGetLastError() == hipSuccess &&  // per-wave sessions (gcm_pw.hip)
+      TG_GEN(launch_gcm_pw)(a, pre, seal, rounds, groups, s))
+    return -1;
+#if TG_TLS13
+  // open: inner-plaintext lengths -> content lengths, after every kernel of this key size
+  if (!seal && hipGetLastError() == hipSuccess) return launch_tls13_unpad(a, rounds, s);
+#endif
   return hipGetLastError() == hipSuccess ? 0 : -1;
 }
 

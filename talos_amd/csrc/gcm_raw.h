@@ -129,6 +129,7 @@ __device__ __forceinline__ bool gcm_raw_job(const BatchArgs& a, uint32_t r,
       RecCtx part = rc;
       const uint32_t e1 = s0 + spw * kWave;  // full blocks only
       part.n = 16u * e1;
+      part.inner = 0;  // a TLS 1.3 seal's type byte lies in the last range
       gcm_blocks<SEAL, ROUNDS, false>(part, S, none, cc, x, s0, lane, laneoff, gl);
       TG_JOB_MARK(3);
       e = nb + 1 - (e1 - kWave + lane);

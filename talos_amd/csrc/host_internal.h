@@ -61,6 +61,9 @@ struct tlsgpu_sessions {
   std::vector<int32_t> kinds;  // host mirror of installed kinds
   std::vector<uint8_t> tag_lens;  // and tag lengths (host pipeline output spans)
   std::vector<const void*> owners;  // SSL* per session for the TaLoS hooks (set_owner)
+  int generation = 0;          // 0: nothing installed yet; 12 / 13: every session is TLS <= 1.2 /
+                               // TLS 1.3 (version 0x0304, RFC 8446 record layout) — set by
+                               // the first install, one generation per table
   bool have[5];                // any session of kind k installed
   std::atomic<unsigned> hints{0};  // TLSGPU_HINT_* (tlsgpu_sessions_hint)
   // EVP contexts: per-slot event of the slot's last install or scrub, so init
@@ -87,14 +90,20 @@ int fail(int code, const char* fmt, ...);
       return tg::fail(TLSGPU_EHIP, "%s: %s", #x, hipGetErrorString(_e));      \
   } while (0)
 
+// tlsgpu_session_params::version of a TLS 1.3 session (include/tlsgpu.h): the
+// RFC 8446 section 5 record layout instead of the TLS 1.2 AEAD layout
+constexpr uint16_t kTls13Version = 0x0304;
 bool valid_params(const tlsgpu_session_params& p);
 
 // engine.cpp.  `kinds`: bit k set = the batch may hold records of AEAD kind k
 // (a kernel is launched only for kinds that are installed AND in the mask; the
-// EVP queue passes the kinds its jobs use).
+// EVP queue passes the kinds its jobs use).  type_out: the descriptors again,
+// writable, when a TLS 1.3 open shall leave each record's inner content type in
+// their type bits (tlsgpu_open_wire).
 int run_batch(tlsgpu_sessions* t, const void* d_descs, uint32_t n, const uint8_t* d_in,
               uint8_t* d_out, int32_t* d_status, hipStream_t s, bool seal, bool raw,
-              const Bounds* bounds = nullptr, unsigned kinds = ~0u, unsigned hints = ~0u);
+              const Bounds* bounds = nullptr, unsigned kinds = ~0u, unsigned hints = ~0u,
+              tlsgpu_record* type_out = nullptr);
 
 inline uint64_t mono_ns() {
   return (uint64_t)std::chrono::duration_cast<std::chrono::nanoseconds>(

@@ -39,9 +39,11 @@ static const long g_host_fail_chunk = [] {
 // The batch-shape hints of a host-resident slice (tlsgpu_sessions_hint): no
 // record short enough for a pack (GCM n <= 992 B, the open length with the
 // explicit nonce and the longest tag), and session runs long enough for the
-// run-at-a-time queue kernel (pws_selected: runs * kPwsRun <= records).
-static unsigned host_hints(const tlsgpu_record* r, uint32_t n, bool seal) {
-  const uint32_t short_max = seal ? 992u : 992u + 8u + 16u;
+// run-at-a-time queue kernel (pws_selected: runs * kPwsRun <= records).  A
+// TLS 1.3 table: 62 blocks of inner plaintext, i.e. 991 B of content on seal
+// (the type byte follows it) and 992 B + the tag on open (no explicit nonce).
+static unsigned host_hints(const tlsgpu_record* r, uint32_t n, bool seal, bool t13) {
+  const uint32_t short_max = t13 ? (seal ? 991u : 992u + 16u) : (seal ? 992u : 992u + 8u + 16u);
   bool shorts = false;
   uint32_t runs = 0;
   for (uint32_t i = 0; i < n; i++) {
@@ -103,14 +105,17 @@ static int host_batch(tlsgpu_sessions* t, bool seal, const tlsgpu_record* h_recs
     *hi = std::min<uint64_t>(r.in_off + (r.len_type & 0xFFFFFFu), in_bytes);
   };
   // the output span exactly (open: the plaintext, explicit nonce and tag
-  // excluded; seal: the fragment): a neighbouring chunk's D2H on another stream
-  // may own the next byte
+  // excluded — for TLS 1.3 the whole inner plaintext, padding included; seal:
+  // the fragment, for TLS 1.3 content + type + tag): a neighbouring chunk's D2H
+  // on another stream may own the next byte
+  const bool t13 = t->generation == 13;
   auto span_out = [&](const tlsgpu_record& r, uint64_t* lo, uint64_t* hi) {
     const uint64_t len = r.len_type & 0xFFFFFFu;
     uint64_t over = 0;
     if (r.session < t->capacity) {
       const int k = t->kinds[r.session];
-      over = (k == TLSGPU_AES_128_GCM || k == TLSGPU_AES_256_GCM ? 8 : 0) + t->tag_lens[r.session];
+      const bool gcm = k == TLSGPU_AES_128_GCM || k == TLSGPU_AES_256_GCM;
+      over = (gcm && !t13 ? 8 : 0) + (gcm && t13 && seal ? 1 : 0) + t->tag_lens[r.session];
     }
     *lo = std::min<uint64_t>(r.out_off, out_bytes);
     *hi = std::min<uint64_t>(r.out_off + (seal ? len + over : (len > over ? len - over : 0)),
@@ -188,7 +193,7 @@ static int host_batch(tlsgpu_sessions* t, bool seal, const tlsgpu_record* h_recs
       if (!in_place && ohi > olo) HIPCHK(hipMemsetAsync(d_out + olo, 0, ohi - olo, hs));
       const Bounds bd = {in_bytes, out_bytes};
       const int rc = run_batch(t, hp.d_recs + a, b - a, d_in, d_out, hp.d_status + a, hs, seal,
-                               false, &bd, ~0u, host_hints(h_recs + a, b - a, seal));
+                               false, &bd, ~0u, host_hints(h_recs + a, b - a, seal, t13));
       if (rc != TLSGPU_OK) return rc;
       HIPCHK(hipEventRecord(ev_done, hs));
       HIPCHK(hipStreamWaitEvent(s_out, ev_done, 0));
@@ -322,11 +327,16 @@ extern "C" int tlsgpu_open_wire(tlsgpu_sessions* t, const tlsgpu_wire_stream* d_
   if (n_streams == 0) return TLSGPU_OK;
   // unused record slots name no session (0xFFFFFFFF): the open kernels skip them
   if (max_records) HIPCHK(hipMemsetAsync(d_recs, 0xFF, sizeof(tlsgpu_record) * (size_t)max_records, s));
+  // (streams of TLS 1.3 sessions: the framing kernel reads the generation from
+  // the session and applies RFC 8446 5.2's header rules)
   if (launch_wire_frame(d_streams, n_streams, d_wire, t->d_sess, t->capacity, max_records, d_recs,
                         d_results, d_total, s))
     return fail(TLSGPU_EHIP, "wire frame launch: %s", hipGetErrorString(hipGetLastError()));
   if (max_records) {
-    int rc = run_batch(t, d_recs, max_records, d_wire, d_wire, d_status, s, false, false);
+    // TLS 1.3: the open's unpad pass leaves every record's inner content type
+    // in its descriptor's type bits, as a TLS 1.2 record's header type is
+    int rc = run_batch(t, d_recs, max_records, d_wire, d_wire, d_status, s, false, false, nullptr,
+                       ~0u, ~0u, d_recs);
     if (rc != TLSGPU_OK) return rc;
   }
   if (launch_wire_finish(n_streams, d_results, d_status, s))
@@ -364,6 +374,17 @@ extern "C" uint64_t tlsgpu_seal_wire_size(int aead, uint32_t data_len, uint32_t 
   const uint64_t nrec = ((uint64_t)data_len + frag - 1) / frag;
   const uint64_t eiv = aead == TLSGPU_AES_128_GCM || aead == TLSGPU_AES_256_GCM ? 8 : 0;
   return data_len + nrec * (5 + eiv + (tag_len ? tag_len : 16));
+}
+
+extern "C" uint64_t tlsgpu_seal_wire_size_v(int aead, uint16_t version, uint32_t data_len,
+                                            uint32_t max_fragment, uint32_t tag_len) {
+  const bool gcm = aead == TLSGPU_AES_128_GCM || aead == TLSGPU_AES_256_GCM;
+  if (version != kTls13Version || !gcm)
+    return tlsgpu_seal_wire_size(aead, data_len, max_fragment, tag_len);
+  // TLS 1.3: header(5) || content || inner type(1) || tag(16) per record, no explicit nonce
+  const uint32_t frag = max_fragment == 0 || max_fragment > 16384 ? 16384 : max_fragment;
+  const uint64_t nrec = ((uint64_t)data_len + frag - 1) / frag;
+  return data_len + nrec * (5 + 1 + 16);
 }
 
 extern "C" int tlsgpu_fill_synthetic(tlsgpu_engine* e, uint8_t* d_out, uint64_t stride,

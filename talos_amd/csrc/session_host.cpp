@@ -195,7 +195,7 @@ bool host_session_image(const tlsgpu_session_params& p, DevSession* s, DevGcmTab
   s->key_len = p.key_len;
   s->fixed_nonce_len = p.fixed_iv_len;
   s->xor_fixed_nonce = p.aead == TLSGPU_CHACHA20_POLY1305;
-  s->nonce_in_record = gcm;
+  s->nonce_in_record = gcm && p.version != 0x0304;  // TLS 1.3: no explicit nonce
   s->version = p.version;
   memcpy(s->fixed_nonce, p.fixed_iv, p.fixed_iv_len);
   if (cc) memcpy(s->chacha_key, p.key, 32);

@@ -206,7 +206,7 @@ __device__ __forceinline__ void install_body(DevSession* __restrict__ sessions,
     s.key_len = p.key_len;
     s.fixed_nonce_len = p.fixed_iv_len;
     s.xor_fixed_nonce = p.aead == TLSGPU_CHACHA20_POLY1305;
-    s.nonce_in_record = gcm;
+    s.nonce_in_record = gcm && p.version != 0x0304;  // TLS 1.3: no explicit nonce
     s.version = p.version;
     for (uint32_t k = 0; k < p.fixed_iv_len; k++) s.fixed_nonce[k] = p.fixed_iv[k];
     if (cc)
@@ -359,9 +359,13 @@ __global__ void check_record_bounds(const tlsgpu_record* __restrict__ recs,
   if (r.session < n_sessions) {
     const DevSession& S = sessions[r.session];
     const uint64_t eiv = S.nonce_in_record ? 8u : 0u, tag = S.tag_len;
+    // a TLS 1.3 seal writes content || type || tag (RFC 8446 5.2)
+    const bool gcm = S.kind == TLSGPU_AES_128_GCM || S.kind == TLSGPU_AES_256_GCM;
+    const uint64_t extra = gcm && eiv == 0 ? 1u : 0u;
     const uint64_t len = r.len_type & 0xFFFFFFu;
     const uint64_t in_len = len;
-    const uint64_t out_len = seal ? len + eiv + tag : (len >= eiv + tag ? len - eiv - tag : 0);
+    const uint64_t out_len =
+        seal ? len + eiv + extra + tag : (len >= eiv + tag ? len - eiv - tag : 0);
     if (r.in_off > in_bytes || in_len > in_bytes - r.in_off || r.out_off > out_bytes ||
         out_len > out_bytes - r.out_off) {
       r.session = 0xFFFFFFFFu;
@@ -380,6 +384,92 @@ int launch_check_bounds(const tlsgpu_record* recs, tlsgpu_record* safe, uint32_t
   hipLaunchKernelGGL(check_record_bounds, dim3((n + 255) / 256), dim3(256), 0, s, recs, safe, n,
                      sessions, n_sessions, in_bytes, out_bytes, seal ? 1 : 0, status, ctl,
                      ctl_words);
+  return hipGetLastError() == hipSuccess ? 0 : -1;
+}
+
+// TLS 1.3 open, the unpad pass (RFC 8446 5.4): the cipher kernels left every
+// record's status = the length m of its decrypted TLSInnerPlaintext (content ||
+// type || zeros) at out_off, or a negative status, BAD_MAC's zero-fill done.
+// Records of TLS 1.3 sessions with status >= 0 get the content length instead:
+// the index of the last non-zero byte (the inner content type sits there), or
+// TLSGPU_REC_NO_CONTENT_TYPE when there is none; the bytes stay as decrypted.
+// One lane per record looks at the last byte, which is the type whenever the
+// sender did not pad; for the others the wave scans backwards, 64 x 16 B per
+// step, one record after the other.  Negative statuses and records of other
+// sessions are left alone.  Launched by the TLS 1.3 GCM launchers only, once
+// per AES key size after that size's kernels (`rounds`: a record is taken in
+// the pass of its own session's key size, so never twice): a TLS 1.2 batch
+// launches nothing new.  type_out != null (tlsgpu_open_wire): the record's
+// inner content type also replaces the type bits of type_out[r].len_type.
+__global__ __launch_bounds__(256) void tls13_unpad_kernel(const tlsgpu_record* recs,  // may be type_out
+                                                          uint32_t n,
+                                                          const DevSession* __restrict__ sessions,
+                                                          uint32_t n_sessions, uint32_t rounds,
+                                                          const uint8_t* __restrict__ out,
+                                                          int32_t* __restrict__ status,
+                                                          tlsgpu_record* type_out) {
+  const uint32_t lane = threadIdx.x & 63;
+  const uint32_t r = blockIdx.x * blockDim.x + threadIdx.x;
+  const uint8_t* p = nullptr;
+  uint32_t m = 0, lt = 0;
+  bool scan = false;
+  // the content length is known: the status, and the type where it is wanted
+  auto done = [&](int32_t cl) {
+    status[r] = cl;
+    if (type_out && cl >= 0) type_out[r].len_type = ((uint32_t)p[cl] << 24) | (lt & 0xFFFFFFu);
+  };
+  if (r < n) {
+    const tlsgpu_record d = recs[r];
+    const int32_t st = status[r];
+    if (d.session < n_sessions && st >= 0) {
+      const DevSession& S = sessions[d.session];
+      const bool gcm = S.kind == TLSGPU_AES_128_GCM || S.kind == TLSGPU_AES_256_GCM;
+      if (gcm && S.nonce_in_record == 0 && S.rounds == rounds) {
+        p = out + d.out_off;
+        m = (uint32_t)st;
+        lt = d.len_type;
+        if (m == 0) done(TLSGPU_REC_NO_CONTENT_TYPE);
+        else if (p[m - 1] != 0) done((int32_t)(m - 1));
+        else scan = true;
+      }
+    }
+  }
+  // padded records: bytes [0, end) still unknown, byte end is zero
+  for (uint64_t todo = __ballot(scan); todo != 0; todo &= todo - 1) {
+    const int k = __builtin_ctzll(todo);
+    const uint64_t pa = ((uint64_t)(uint32_t)__shfl((int)((uintptr_t)p >> 32), k) << 32) |
+                        (uint32_t)__shfl((int)(uint32_t)(uintptr_t)p, k);
+    const uint8_t* pk = reinterpret_cast<const uint8_t*>(pa);
+    int32_t found = -1;
+    for (uint32_t end = (uint32_t)__shfl((int)m, k) - 1; end != 0 && found < 0;
+         end -= min(end, 16u * kWave)) {
+      int32_t idx = -1;
+      if (16u * lane < end) {  // this lane's piece [lo, hi), nearest the end for lane 0
+        const uint32_t hi = end - 16u * lane, lo = hi > 16u ? hi - 16u : 0u;
+        uint32_t v[4];
+        if (hi - lo == 16u) load16_any(pk + lo, v);
+        else load16_upto(pk + lo, hi - lo, v);  // whole dwords: bytes past the piece masked here
+#pragma unroll
+        for (int w = 3; w >= 0; w--) {
+          const int32_t b = (int32_t)(hi - lo) - 4 * w;
+          v[w] &= b >= 4 ? 0xFFFFFFFFu : (b <= 0 ? 0u : ((1u << (8 * b)) - 1u));
+        }
+#pragma unroll
+        for (int w = 3; w >= 0; w--)
+          if (idx < 0 && v[w] != 0) idx = (int32_t)(lo + 4 * w + (31 - __builtin_clz(v[w])) / 8);
+      }
+      const uint64_t has = __ballot(idx >= 0);
+      if (has) found = __shfl(idx, __builtin_ctzll(has));  // the lowest lane holds the last one
+    }
+    if ((int)lane == k) done(found >= 0 ? found : TLSGPU_REC_NO_CONTENT_TYPE);
+  }
+}
+
+int launch_tls13_unpad(const BatchArgs& a, int rounds, hipStream_t s) {
+  if (a.n == 0) return 0;
+  hipLaunchKernelGGL(tls13_unpad_kernel, dim3((a.n + 255) / 256), dim3(256), 0, s,
+                     reinterpret_cast<const tlsgpu_record*>(a.descs), a.n, a.sessions, a.n_sessions,
+                     (uint32_t)rounds, a.out, a.status, a.type_out);
   return hipGetLastError() == hipSuccess ? 0 : -1;
 }
 

@@ -23,7 +23,8 @@ struct alignas(16) DevSession {
   uint32_t key_len;
   uint32_t fixed_nonce_len;   // 4 / 12 / 0
   uint32_t xor_fixed_nonce;   // ChaCha RFC 7905
-  uint32_t nonce_in_record;   // GCM explicit nonce
+  uint32_t nonce_in_record;   // GCM explicit nonce (TLS 1.2); 0 for a TLS 1.3 GCM session,
+                              // which is how the GCM kernels tell the two apart (gcm_tls13)
   uint32_t version;           // TLS version for the AAD
   uint8_t fixed_nonce[16];
   uint32_t rk[60];            // AES round keys, little-endian column words
@@ -221,6 +222,12 @@ struct BatchArgs {
                                     // *n_pieces == 0: the count ranges)
   unsigned long long* wg_times;     // diagnostic (TLSGPU_WG_TIMES=1), normally null: per
                                     // workgroup {start, end (s_memrealtime), rlo, rhi}
+  uint32_t tls13;                   // the table's sessions are TLS 1.3: the GCM launchers run
+                                    // the kernels compiled for that record layout (their *13
+                                    // twins) and, after an open, the unpad pass
+  tlsgpu_record* type_out;          // TLS 1.3 open, non-null (tlsgpu_open_wire: the engine's own
+                                    // descriptors): the unpad pass also moves every opened
+                                    // record's inner content type into len_type's type bits
 };
 
 // Work-balanced ranges (round 5): a record's work for the cut — its payload
@@ -282,6 +289,20 @@ int launch_gcm_queue_b16(const BatchArgs& a, const RecPre* pre, bool seal, int r
                          hipStream_t s);
 int launch_gcm_pw(const BatchArgs& a, const RecPre* pre, bool seal, int rounds, int groups,
                   hipStream_t s);
+// The same launchers for TLS 1.3 session tables (gcm_kernels13.hip, gcm_queue13.hip,
+// gcm_pw13.hip: the kernels compiled for the RFC 8446 record layout).  The host
+// units call the launchers above, which forward here when a.tls13 is set.
+int launch_gcm13(const BatchArgs& a, bool seal, bool raw, int rounds, int groups, hipStream_t s);
+int launch_gcm_split13(const BatchArgs& a, bool seal, int rounds, hipStream_t s);
+int launch_gcm_prep13(const BatchArgs& a, RecPre* pre, bool seal, int rounds, hipStream_t s);
+int launch_gcm_queue13(const BatchArgs& a, const RecPre* pre, bool seal, int rounds, int groups,
+                       hipStream_t s);
+int launch_gcm_pw13(const BatchArgs& a, const RecPre* pre, bool seal, int rounds, int groups,
+                    hipStream_t s);
+// TLS 1.3 open: inner-plaintext lengths in a.status -> content lengths, for the
+// records of sessions with `rounds` AES rounds (session_kernels.hip; called by
+// the TLS 1.3 launchers after their kernels, once per key size)
+int launch_tls13_unpad(const BatchArgs& a, int rounds, hipStream_t s);
 int launch_gcm_stream(const DevSession* sessions, const DevGcmTables* tables, uint32_t session,
                       GcmStream* st, const GcmStreamOp* ops, uint32_t nops, hipStream_t s);
 int launch_gcm_hy10(const BatchArgs& a, const RecPre* pre, bool seal, int bs_waves, int groups,

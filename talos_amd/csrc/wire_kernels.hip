@@ -24,7 +24,11 @@ constexpr uint32_t kMaxEncrypted = 256 + 64 + 16384;  // SSL3_RT_MAX_ENCRYPTED_L
 constexpr uint32_t kMaxPlain = 16384;                 // SSL3_RT_MAX_PLAIN_LENGTH
 constexpr uint32_t kDefaultRbuf = 16384 + 320 + 5 + 3;  // ssl3_setup_read_buffer (s3_both.c:667-675)
 constexpr int32_t kAlertBadRecordMac = 20, kAlertDecryptionFailed = 21, kAlertRecordOverflow = 22,
-                  kAlertProtocolVersion = 70;
+                  kAlertProtocolVersion = 70, kAlertUnexpectedMessage = 10;
+// TLS 1.3 (RFC 8446 5.2): every protected record's outer type is
+// application_data and its fragment is at most 2^14 + 256 bytes
+constexpr uint32_t kMaxEncrypted13 = 16384 + 256;
+constexpr uint32_t kAppData = 23;
 
 struct WireWalk {
   uint32_t records;   // complete records that pass the header checks
@@ -98,12 +102,14 @@ __device__ __forceinline__ uint32_t uni(uint32_t v) { return __builtin_amdgcn_re
 // (wave-uniform arguments), bulk(index, k0, m, base, stride, header) for m
 // records accepted at once from the speculative headers — lane k in
 // [k0, k0 + m) holds record index + k - k0 at base + k * stride.  Whole wave,
-// `win` = the wave's kWin LDS bytes.
+// `win` = the wave's kWin LDS bytes.  t13: the stream's session table is TLS 1.3
+// (outer type 23 or unexpected_message; the TLS 1.3 fragment bound).
 template <class Visit, class Bulk>
 __device__ __forceinline__ WireWalk wire_walk(const tlsgpu_wire_stream& st, const uint8_t* w,
-                                              uint32_t limit, uint8_t* win, uint32_t lane,
+                                              uint32_t limit, uint8_t* win, uint32_t lane, bool t13,
                                               Visit&& visit, Bulk&& bulk) {
   WireWalk r = {0, 0, 0};
+  const uint32_t max_enc = t13 ? kMaxEncrypted13 : kMaxEncrypted;
   const uint32_t rbuf = st.rbuf_len ? st.rbuf_len : kDefaultRbuf;
   const uint32_t len = st.wire_len;
   uint32_t pos = 0, stride = 0;
@@ -120,7 +126,8 @@ __device__ __forceinline__ WireWalk wire_walk(const tlsgpu_wire_stream& st, cons
       const bool ok = lane >= cnext && ck + kHdr <= len &&
                       ((st.flags & TLSGPU_WIRE_FIRST_PACKET) || cand.ver == st.version) &&
                       (cand.ver >> 8) == 3 && cand.len <= rbuf - kHdr &&
-                      ck + kHdr + cand.len <= len && cand.len <= kMaxEncrypted &&
+                      ck + kHdr + cand.len <= len && cand.len <= max_enc &&
+                      (!t13 || cand.type == kAppData) &&
                       cand.len + kHdr == cstride && r.records + (lane - cnext) < limit;
       const uint64_t run = ~__ballot(ok) >> cnext;  // bit j: lane cnext + j fails
       const uint32_t m = run ? (uint32_t)__builtin_ctzll(run) : 64u - cnext;
@@ -161,12 +168,16 @@ __device__ __forceinline__ WireWalk wire_walk(const tlsgpu_wire_stream& st, cons
       r.alert = -1;
       break;
     }
+    if (t13 && h.type != kAppData) {  // RFC 8446 5.2: opaque_type is application_data
+      r.alert = kAlertUnexpectedMessage;
+      break;
+    }
     if (h.len > rbuf - kHdr) {  // :337-341
       r.alert = kAlertRecordOverflow;
       break;
     }
     if (pos + kHdr + h.len > len) break;  // fragment not complete yet
-    if (h.len > kMaxEncrypted) {  // :376-380
+    if (h.len > max_enc) {  // :376-380
       r.alert = kAlertRecordOverflow;
       break;
     }
@@ -198,9 +209,15 @@ __global__ __launch_bounds__(64 * kFrameWaves) void wire_frame_kernel(
   uint2* list = lists[wave];
   tlsgpu_wire_stream st = {};
   WireWalk walk = {};
+  bool t13 = false;  // the stream's session is TLS 1.3: a GCM session without an explicit nonce
   if (active) {
     st = streams[s];
-    walk = wire_walk(st, wire + st.wire_off, 0xFFFFFFFFu, wins[wave], lane,
+    if (st.session < n_sessions) {
+      const uint32_t kind = sessions[st.session].kind;
+      t13 = (kind == TLSGPU_AES_128_GCM || kind == TLSGPU_AES_256_GCM) &&
+            sessions[st.session].nonce_in_record == 0;
+    }
+    walk = wire_walk(st, wire + st.wire_off, 0xFFFFFFFFu, wins[wave], lane, t13,
                      [&](uint32_t i, uint32_t pos, const Hdr& h) {
                        if (lane == 0 && i < kList) list[i] = make_uint2(pos, (h.type << 24) | h.len);
                      },
@@ -231,12 +248,12 @@ __global__ __launch_bounds__(64 * kFrameWaves) void wire_frame_kernel(
   } else if (first + n > max_records) {
     n = max_records - first;
   }
-  // explicit nonce length of the session's AEAD (GCM 8, ChaCha 0); an unknown
+  // explicit nonce length of the session's AEAD (GCM 8, ChaCha and TLS 1.3 0); an unknown
   // session still gets descriptors, which the open kernels leave PUBLIC_INVALID
   uint32_t eiv = 0;
   if (st.session < n_sessions) {
     const uint32_t kind = sessions[st.session].kind;
-    eiv = (kind == TLSGPU_AES_128_GCM || kind == TLSGPU_AES_256_GCM) ? 8u : 0u;
+    eiv = !t13 && (kind == TLSGPU_AES_128_GCM || kind == TLSGPU_AES_256_GCM) ? 8u : 0u;
   }
   if (walk.records <= kList) {  // descriptors from the list, 64 per wave store
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
@@ -269,7 +286,7 @@ __global__ __launch_bounds__(64 * kFrameWaves) void wire_frame_kernel(
       if (lane < held) recs[first + upto - held + lane] = d;
       held = 0;
     };
-    const WireWalk w2 = wire_walk(st, w, n, wins[wave], lane, [&](uint32_t i, uint32_t pos, const Hdr& h) {
+    const WireWalk w2 = wire_walk(st, w, n, wins[wave], lane, t13, [&](uint32_t i, uint32_t pos, const Hdr& h) {
       if (lane == held) {
         d.in_off = st.wire_off + pos + kHdr;
         d.out_off = d.in_off + eiv;
@@ -311,7 +328,10 @@ __global__ __launch_bounds__(64 * kFrameWaves) void wire_frame_kernel(
 
 // One wave per stream: the statuses of 64 records per load, the first failing
 // record found with a ballot (s3_pkt.c alert order: the first failure wins,
-// later records are not delivered).
+// later records are not delivered).  A TLS 1.3 record without a content type
+// (TLSGPU_REC_NO_CONTENT_TYPE, from the open's unpad pass, which also left the
+// inner content types in the descriptors) ends its stream with
+// unexpected_message.
 __global__ __launch_bounds__(256) void wire_finish_kernel(uint32_t n_streams,
                                                           tlsgpu_wire_result* __restrict__ results,
                                                           int32_t* __restrict__ status) {
@@ -332,6 +352,7 @@ __global__ __launch_bounds__(256) void wire_finish_kernel(uint32_t n_streams,
     const int32_t alert = !in ? 0
                           : st == TLSGPU_REC_BAD_MAC        ? kAlertBadRecordMac
                           : st == TLSGPU_REC_PUBLIC_INVALID ? kAlertDecryptionFailed
+                          : st == TLSGPU_REC_NO_CONTENT_TYPE ? kAlertUnexpectedMessage
                           : st > (int32_t)kMaxPlain         ? kAlertRecordOverflow
                                                             : 0;
     const uint64_t bad = __ballot(alert != 0);
@@ -396,16 +417,20 @@ __global__ __launch_bounds__(256) void wire_seal_frame_kernel(
   res.first = first;
   if (nrec) {
     const DevSession& S = sessions[st.session];
-    const uint32_t over = (S.nonce_in_record ? 8u : 0u) + S.tag_len;  // eivlen + tag
+    // TLS 1.3 (a GCM session without an explicit nonce): the fragment is content ||
+    // inner type || tag under the header 17 03 03 (RFC 8446 5.2); st.type is the inner type
+    const bool t13 = (S.kind == TLSGPU_AES_128_GCM || S.kind == TLSGPU_AES_256_GCM) &&
+                     S.nonce_in_record == 0;
+    const uint32_t over = (S.nonce_in_record ? 8u : 0u) + (t13 ? 1u : 0u) + S.tag_len;  // eivlen + tag
     uint64_t pos = st.wire_off;
     for (uint32_t k = 0; k < nrec; k++) {
       const uint32_t len = min(frag, st.data_len - k * frag);
       const uint32_t L = len + over;  // the length field (s3_pkt.c:733)
       if (pos <= wire_bytes && (uint64_t)kHdr + L <= wire_bytes - pos) {  // no wrap
         uint8_t* h = wire + pos;
-        h[0] = st.type;
-        h[1] = (uint8_t)(st.version >> 8);
-        h[2] = (uint8_t)st.version;
+        h[0] = t13 ? (uint8_t)kAppData : st.type;
+        h[1] = t13 ? 3 : (uint8_t)(st.version >> 8);
+        h[2] = t13 ? 3 : (uint8_t)st.version;
         h[3] = (uint8_t)(L >> 8);
         h[4] = (uint8_t)L;
       }

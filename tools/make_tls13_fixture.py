@@ -1,0 +1,138 @@
+#!/usr/bin/env python3
+"""Capture TLS 1.3 records from a real connection: tests/golden/tls13_wire.json.
+
+Python's ssl module (the system OpenSSL) runs a TLS 1.3 handshake between a
+client and a server over two MemoryBIOs with tests/golden/server.pem, then
+each side writes application data of several lengths, among them one write of
+more than 16 KiB (several records).  The key log gives CLIENT_TRAFFIC_SECRET_0
+and SERVER_TRAFFIC_SECRET_0; HKDF-Expand-Label (tests/tls13_helper.py) gives
+each direction's write key and IV.  Every protected record of either
+direction that opens under those keys at the running sequence number is
+written out: suite, key, IV, the lengths of the writes and per record seq, wire
+bytes (header + fragment), inner content type and content (byte strings in
+base64).  The server's NewSessionTicket
+records (inner type 22) are part of its direction; records under the
+handshake keys do not open and are left out.
+
+The AEAD used to open the records here is the oracle's; the test suite then
+checks the helper's seal against the captured bytes, and the engine against
+both.  usage: tools/make_tls13_fixture.py [out.json]
+"""
+import base64
+import json
+import os
+import ssl
+import sys
+import tempfile
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path[:0] = [os.path.join(ROOT, "oracle"), os.path.join(ROOT, "tests")]
+import pyoracle as po  # noqa: E402
+import tls13_helper as t13  # noqa: E402
+
+PEM = os.path.join(ROOT, "tests", "golden", "server.pem")
+CLIENT_WRITES = [1, 16, 1008]        # small: the fixture is committed
+SERVER_WRITES = [49, 992, 16385]     # the last one goes out as two records
+
+
+def pattern(n: int, salt: int) -> bytes:
+    return bytes((7 * i + 13 * salt + (i >> 8)) & 0xFF for i in range(n))
+
+
+def main(out_path: str) -> None:
+    keylog = tempfile.NamedTemporaryFile(suffix=".keylog", delete=False)
+    keylog.close()
+    sctx = ssl.SSLContext(ssl.PROTOCOL_TLS_SERVER)
+    sctx.set_ciphers("ALL:@SECLEVEL=0")   # the test certificate is old
+    sctx.load_cert_chain(PEM)
+    sctx.minimum_version = ssl.TLSVersion.TLSv1_3
+    cctx = ssl.SSLContext(ssl.PROTOCOL_TLS_CLIENT)
+    cctx.set_ciphers("ALL:@SECLEVEL=0")
+    cctx.check_hostname = False
+    cctx.verify_mode = ssl.CERT_NONE
+    cctx.minimum_version = ssl.TLSVersion.TLSv1_3
+    cctx.keylog_filename = keylog.name
+    c_in, c_out, s_in, s_out = (ssl.MemoryBIO() for _ in range(4))
+    cli = cctx.wrap_bio(c_in, c_out, server_side=False)
+    srv = sctx.wrap_bio(s_in, s_out, server_side=True)
+    wire = {"client": b"", "server": b""}
+
+    def pump():
+        moved = False
+        for name, src, dst in (("client", c_out, s_in), ("server", s_out, c_in)):
+            data = src.read()
+            if data:
+                wire[name] += data
+                dst.write(data)
+                moved = True
+        return moved
+
+    done = [False, False]
+    for _ in range(20):
+        for k, side in enumerate((cli, srv)):
+            if not done[k]:
+                try:
+                    side.do_handshake()
+                    done[k] = True
+                except ssl.SSLWantReadError:
+                    pass
+        pump()
+        if all(done):
+            break
+    assert all(done) and cli.version() == "TLSv1.3", cli.version()
+    suite = cli.cipher()[0]
+    writes = {"client": [], "server": []}
+    for name, side, peer, lens in (("client", cli, srv, CLIENT_WRITES),
+                                   ("server", srv, cli, SERVER_WRITES)):
+        for k, n in enumerate(lens):
+            data = pattern(n, k + (100 if name == "server" else 0))
+            side.write(data)
+            pump()
+            got = b""
+            while len(got) < n:
+                try:
+                    got += peer.read(n - len(got))
+                except ssl.SSLWantReadError:
+                    break
+            assert got == data
+            writes[name].append(n)   # the records' contents concatenate to the writes
+    secrets = {}
+    for line in open(keylog.name):
+        f = line.split()
+        if len(f) == 3:
+            secrets[f[0]] = bytes.fromhex(f[2])
+    os.unlink(keylog.name)
+    orc = po.Oracle()
+    fixture = {"suite": suite, "openssl": ssl.OPENSSL_VERSION, "directions": []}
+    for name, label in (("client", "CLIENT_TRAFFIC_SECRET_0"), ("server", "SERVER_TRAFFIC_SECRET_0")):
+        kind, key, iv = t13.traffic_keys(secrets[label], suite)
+        ctx = orc.aead(kind, key)
+        seq, recs = 0, []
+        for hdr, frag in t13.split_records(wire[name]):
+            if hdr[0] != t13.APPLICATION_DATA:
+                continue   # ClientHello / ServerHello / compatibility ChangeCipherSpec
+            st, inner = t13.open_fragment(orc, ctx, iv, seq, frag)
+            if st < 0:
+                assert not recs, "a record after the first application-key record did not open"
+                continue   # under the handshake traffic keys
+            recs.append({"seq": seq, "wire": base64.b64encode(hdr + frag).decode(),
+                         "inner_type": inner[st],
+                         "content": base64.b64encode(inner[:st]).decode()})
+            seq += 1
+        assert recs
+        fixture["directions"].append({"name": name, "key": key.hex(), "iv": iv.hex(),
+                                      "records": recs, "writes": writes[name]})
+    with open(out_path, "w") as f:   # one record per line
+        recs = [d.pop("records") for d in fixture["directions"]]
+        head = json.dumps(fixture)
+        for d, r in zip(fixture["directions"], recs):
+            d["records"] = r
+            one = json.dumps({k: v for k, v in d.items() if k != "records"})
+            head = head.replace(one, one[:-1] + ', "records": [\n' +
+                                ",\n".join(json.dumps(x) for x in r) + "]}")
+        f.write(head + "\n")
+    print(out_path, suite, {d["name"]: len(d["records"]) for d in fixture["directions"]})
+
+
+if __name__ == "__main__":
+    main(sys.argv[1] if len(sys.argv) > 1 else t13.GOLDEN)
