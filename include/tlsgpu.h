@@ -1,7 +1,8 @@
 /*
  * tlsgpu.h — MI355X-native TLS record bulk-cipher engine: batch C ABI
  * (TLS 1.2 AEAD records as LibreSSL 2.4.1 protects them, and TLS 1.3 AES-GCM
- * records, RFC 8446 5.2-5.4: see "TLS 1.3 sessions" below).
+ * and ChaCha20-Poly1305 records, RFC 8446 5.2-5.4: see "TLS 1.3 sessions"
+ * below).
  *
  * This is the GPU extension that sits beside the drop-in EVP_AEAD ABI
  * (include/tlsgpu_evp.h).  It has no reference counterpart; it batches the
@@ -35,7 +36,15 @@ enum tlsgpu_aead {
 	TLSGPU_AES_128_GCM = 1,
 	TLSGPU_AES_256_GCM = 2,
 	TLSGPU_CHACHA20_POLY1305 = 3,	/* RFC 7539/7905, 12-byte nonce */
-	TLSGPU_CHACHA20_POLY1305_OLD = 4	/* draft-agl, 8-byte nonce */
+	TLSGPU_CHACHA20_POLY1305_OLD = 4,	/* draft-agl, 8-byte nonce */
+	/* TLS_CHACHA20_POLY1305_SHA256 in the TLS 1.3 record layout (RFC 8446
+	 * 5.2-5.4): the cipher and the nonce are kind 3's, the record layout is
+	 * not.  The layout is carried by the kind, not by the version alone: _OLD
+	 * already names a record layout rather than a cipher, the ChaCha kernels
+	 * dispatch on the session's kind, and a caller who only bumps a TLS 1.2
+	 * ChaCha session's version to 0x0304 gets TLSGPU_EINVAL, not silently
+	 * different AAD.  Valid only with version 0x0304. */
+	TLSGPU_CHACHA20_POLY1305_TLS13 = 5
 };
 
 /* Return codes. */
@@ -87,7 +96,8 @@ enum tlsgpu_aead {
  * seq is the record's 64-bit sequence number (read_sequence/write_sequence
  * before tls1_record_sequence_increment, t1_enc.c:258-266,841-847).
  *
- * TLS 1.3 sessions (version 0x0304, AES-GCM; RFC 8446 5.2-5.4).  The record
+ * TLS 1.3 sessions (version 0x0304; AES-GCM kinds or
+ * TLSGPU_CHACHA20_POLY1305_TLS13; RFC 8446 5.2-5.4).  The record
  * nonce is fixed_iv(12) XOR (0^32 || BE64(seq)), there is no explicit nonce,
  * and the AAD is the record header 0x17 0x03 0x03 BE16(ciphertext length with
  * the tag); the descriptor's type bits do not enter it.
@@ -105,8 +115,9 @@ enum tlsgpu_aead {
  *       decrypted).  TLSGPU_REC_BAD_MAC zero-fills all length - 16 bytes;
  *       length < 16 gives TLSGPU_REC_PUBLIC_INVALID.
  * TLSGPU_MAX_RECORD bounds the inner plaintext, and the bounds rule of
- * TLSGPU_REC_OUT_OF_BOUNDS uses these spans.  Limits: no ChaCha20-Poly1305, no
- * padding on seal, post-handshake records only (the compatibility
+ * TLSGPU_REC_OUT_OF_BOUNDS uses these spans.  All of this holds for the three
+ * TLS 1.3 kinds alike (ChaCha20-Poly1305: RFC 7905's nonce is RFC 8446's).
+ * Limits: no padding on seal, post-handshake records only (the compatibility
  * ChangeCipherSpec of a handshake is the caller's to skip). */
 typedef struct tlsgpu_record {
 	uint64_t in_off;
@@ -124,17 +135,20 @@ typedef struct tlsgpu_session_params {
 	int32_t aead;			/* enum tlsgpu_aead */
 	uint32_t key_len;		/* 16 or 32 */
 	uint8_t key[32];
-	uint32_t fixed_iv_len;		/* 4 (GCM), 12 (ChaCha, TLS 1.3 GCM), 0 (ChaCha old) */
+	uint32_t fixed_iv_len;		/* 4 (GCM), 12 (ChaCha, every TLS 1.3 kind), 0 (ChaCha old) */
 	uint8_t fixed_iv[12];
 	uint32_t tag_len;		/* 0 = default 16 (EVP_AEAD_DEFAULT_TAG_LENGTH) */
 	uint16_t version;		/* s->version, e.g. 0x0303; 0x0304: a TLS 1.3 session */
 	uint16_t reserved;
 } tlsgpu_session_params;
-/* A TLS 1.3 session is aead = TLSGPU_AES_128_GCM / _256_GCM, version = 0x0304,
- * fixed_iv_len = 12 (the traffic secret's write IV; the key is its write key,
- * and seq starts at 0 for every key), tag_len 16 (0 means 16).  0x0304 with
- * any other fixed_iv_len, tag_len or with a ChaCha kind is TLSGPU_EINVAL at
- * install.  Every other version behaves as before.
+/* A TLS 1.3 session is aead = TLSGPU_AES_128_GCM / _256_GCM /
+ * TLSGPU_CHACHA20_POLY1305_TLS13, version = 0x0304, fixed_iv_len = 12 (the
+ * traffic secret's write IV; the key is its write key, and seq starts at 0 for
+ * every key), tag_len 16 (0 means 16).  0x0304 with any other fixed_iv_len,
+ * tag_len or with a TLS 1.2 ChaCha kind (3, 4) is TLSGPU_EINVAL at install, and
+ * so is TLSGPU_CHACHA20_POLY1305_TLS13 with any other version, a key_len other
+ * than 32, another fixed_iv_len or tag_len.  Every other version behaves as
+ * before.  The three TLS 1.3 kinds share tables and batches.
  * One session table holds one generation: the GCM kernels are compiled once
  * per record layout (carrying the layout as per-session data cost the TLS 1.2
  * queue kernel's pack variants spilled registers), so the
@@ -358,7 +372,8 @@ int tlsgpu_group_sync(tlsgpu_group *g);
  * truncated at a record boundary (their `records`/`consumed` say how far).
  * d_total receives the number of descriptors written.  Asynchronous.
  *
- * Streams of a TLS 1.3 table (the caller passes version = 0x0303, the legacy
+ * Streams of a TLS 1.3 table, AES-GCM and ChaCha20-Poly1305 sessions alike
+ * (the caller passes version = 0x0303, the legacy
  * record version): the outer type must be 23, else unexpected_message (10); a
  * fragment above 16384 + 256 B gives record_overflow (22), one below 16 B
  * decryption_failed (21); records are opened in place at the fragment start.
@@ -407,7 +422,7 @@ int tlsgpu_open_wire(tlsgpu_sessions *t, const tlsgpu_wire_stream *d_streams,
  * status each.  data_bytes / wire_bytes bound the buffers
  * (TLSGPU_REC_OUT_OF_BOUNDS).  tlsgpu_seal_wire_size gives a stream's wire
  * bytes.  Asynchronous.
- * A TLS 1.3 session: each fragment (<= max_fragment <= 16384) goes out as the
+ * A TLS 1.3 session of any kind: each fragment (<= max_fragment <= 16384) goes out as the
  * header 17 03 03 BE16(len + 17) and ciphertext(content || type) || tag, with
  * stream.type as the inner type; next_seq and wire_len follow that framing
  * (tlsgpu_seal_wire_size_v). */
@@ -436,12 +451,16 @@ int tlsgpu_seal_wire(tlsgpu_sessions *t, const tlsgpu_write_stream *d_streams,
     size_t wire_bytes, uint32_t max_records, tlsgpu_record *d_recs, int32_t *d_status,
     tlsgpu_write_result *d_results, uint32_t *d_total, void *stream);
 /* Wire bytes of one stream: ceil(len / frag) records of 5 + explicit nonce
- * (8 for GCM, 0 for ChaCha) + fragment + tag_len bytes (0 when len == 0). */
+ * (8 for GCM, 0 for ChaCha) + fragment + tag_len bytes (0 when len == 0).
+ * TLSGPU_CHACHA20_POLY1305_TLS13 exists in TLS 1.3 only, so it gets the TLS 1.3
+ * framing of tlsgpu_seal_wire_size_v here too. */
 uint64_t tlsgpu_seal_wire_size(int aead, uint32_t data_len, uint32_t max_fragment,
     uint32_t tag_len);
-/* The same for a session of `version`: 0x0304 with an AES-GCM kind is TLS 1.3
- * framing, ceil(len / frag) records of 5 + fragment + 1 (inner type) + 16;
- * anything else is tlsgpu_seal_wire_size. */
+/* The same for a session of `version`: 0x0304 with an AES-GCM kind, and
+ * TLSGPU_CHACHA20_POLY1305_TLS13 with any version, is TLS 1.3 framing,
+ * ceil(len / frag) records of 5 + fragment + 1 (inner type) + 16; anything
+ * else is tlsgpu_seal_wire_size (TLSGPU_CHACHA20_POLY1305 with 0x0304, which
+ * no install accepts, keeps the TLS 1.2 arithmetic). */
 uint64_t tlsgpu_seal_wire_size_v(int aead, uint16_t version, uint32_t data_len,
     uint32_t max_fragment, uint32_t tag_len);
 

@@ -1,16 +1,19 @@
 #!/usr/bin/env python3
 """What TLS 1.3 record protection costs next to TLS 1.2 on the same build and
-box: a B-shaped batch (64 Ki x 16 KiB records, 1,024 sessions, AES-128-GCM) and
-a D-shaped one (256 Ki records, Zipf lengths 64..16384, 1,024 sessions,
-AES-256-GCM), sealed and opened as TLS 1.2 and as TLS 1.3 sessions with the
-same keys, contents and sequence numbers.  Timed between events on the engine
+box: a B-shaped batch (64 Ki x 16 KiB records, 1,024 sessions, AES-128-GCM), a
+D-shaped one (256 Ki records, Zipf lengths 64..16384, 1,024 sessions,
+AES-256-GCM) and a C-shaped one (1 Mi x 1,400-byte records, 4,096 sessions,
+ChaCha20-Poly1305: kind 3 / 0x0303 against kind 5 / 0x0304), sealed and opened
+as TLS 1.2 and as TLS 1.3 sessions with the same keys, contents and sequence
+numbers.  Timed between events on the engine
 stream as bench.py does (warm-up launches, then `steps` launches between two
 events); prints one JSON line per (shape, generation, op) and the ratios.
 
-    python scripts/tls13_cost.py [--shape B|D|BD] [--gen 12|13|both] [--steps K] [--warmup W]
+    python scripts/tls13_cost.py [--shape B|C|D|BD|...] [--gen 12|13|both] [--steps K] [--warmup W]
 
 Under `rocprofv3 --kernel-trace --stats -- python scripts/tls13_cost.py --gen 13
---steps 3` the stats list tg::tls13_unpad_kernel, the unpad pass's own time.
+--steps 3` the stats list tg::tls13_unpad_kernel, the unpad pass's own time
+(--shape C: the ChaCha sessions' pass).
 """
 import argparse
 import json
@@ -25,17 +28,22 @@ import talos_amd as ta  # noqa: E402
 from talos_amd.workload import KEY_TAG, IV_TAG, fill_bytes, zipf_lengths  # noqa: E402
 
 SHAPES = {"B": (ta.AES_128_GCM, 65536, 1024, None, 0x5EED0001),
-          "D": (ta.AES_256_GCM, 1 << 18, 1024, "zipf", 0x5EED0003)}
+          "D": (ta.AES_256_GCM, 1 << 18, 1024, "zipf", 0x5EED0003),
+          "C": (ta.CHACHA20_POLY1305, 1 << 20, 4096, 1400, 0x5EED0002)}
 GIB = float(1 << 30)
 
 
 def run(engine, shape, gen, steps, warmup):
     kind, n, nsess, dist, seed = SHAPES[shape]
     t13 = gen == 13
-    lens = (np.full(n, 16384, dtype=np.int64) if dist is None else zipf_lengths(n, seed))
-    eiv, extra = (0, 1) if t13 else (8, 0)
+    lens = (np.full(n, 16384, dtype=np.int64) if dist is None
+            else zipf_lengths(n, seed) if dist == "zipf" else np.full(n, dist, dtype=np.int64))
+    chacha = kind == ta.CHACHA20_POLY1305
+    if chacha and t13:
+        kind = ta.CHACHA20_POLY1305_TLS13     # the same cipher, key and 12-byte IV
+    eiv, extra = (0, 1) if t13 else (0 if chacha else 8, 0)
     params = [ta.SessionParams(kind, fill_bytes(seed ^ KEY_TAG, s, ta.KEY_LEN[kind]),
-                               fill_bytes(seed ^ IV_TAG, s, 12 if t13 else 4),
+                               fill_bytes(seed ^ IV_TAG, s, 12 if t13 or chacha else 4),
                                version=0x0304 if t13 else 0x0303) for s in range(nsess)]
     table = ta.SessionTable(engine, nsess)
     table.install(0, params)

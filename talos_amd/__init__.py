@@ -1,6 +1,7 @@
 """talos_amd — MI355X-native TLS record bulk-cipher engine (Python host side):
-TLS 1.2 AEAD records and TLS 1.3 AES-GCM records (``SessionParams(...,
-version=0x0304)`` with the 12-byte write IV; include/tlsgpu.h).
+TLS 1.2 AEAD records and TLS 1.3 records, AES-GCM (``SessionParams(...,
+version=0x0304)`` with the 12-byte write IV) and ChaCha20-Poly1305
+(``CHACHA20_POLY1305_TLS13``, the same version and IV; include/tlsgpu.h).
 
 The engine itself is ``libtlsgpu.so`` (HIP kernels for gfx950 behind a C ABI,
 ``include/tlsgpu.h`` + the drop-in EVP_AEAD ABI ``include/tlsgpu_evp.h``).
@@ -32,13 +33,17 @@ LIBPATH = os.environ.get("TLSGPU_LIBRARY") or os.path.join(HERE, "libtlsgpu.so")
 INCLUDE = os.path.join(ROOT, "include")
 
 AES_128_GCM, AES_256_GCM, CHACHA20_POLY1305, CHACHA20_POLY1305_OLD = 1, 2, 3, 4
+# TLS_CHACHA20_POLY1305_SHA256 in the TLS 1.3 record layout; version 0x0304 only
+CHACHA20_POLY1305_TLS13 = 5
 AEAD_NAMES = {"aes-128-gcm": AES_128_GCM, "aes-256-gcm": AES_256_GCM,
               "chacha20-poly1305": CHACHA20_POLY1305,
               "chacha20-poly1305-old": CHACHA20_POLY1305_OLD}
-KEY_LEN = {AES_128_GCM: 16, AES_256_GCM: 32, CHACHA20_POLY1305: 32, CHACHA20_POLY1305_OLD: 32}
-FIXED_IV_LEN = {AES_128_GCM: 4, AES_256_GCM: 4, CHACHA20_POLY1305: 12, CHACHA20_POLY1305_OLD: 0}
+KEY_LEN = {AES_128_GCM: 16, AES_256_GCM: 32, CHACHA20_POLY1305: 32, CHACHA20_POLY1305_OLD: 32,
+           CHACHA20_POLY1305_TLS13: 32}
+FIXED_IV_LEN = {AES_128_GCM: 4, AES_256_GCM: 4, CHACHA20_POLY1305: 12, CHACHA20_POLY1305_OLD: 0,
+                CHACHA20_POLY1305_TLS13: 12}
 EXPLICIT_NONCE_LEN = {AES_128_GCM: 8, AES_256_GCM: 8, CHACHA20_POLY1305: 0,
-                      CHACHA20_POLY1305_OLD: 0}
+                      CHACHA20_POLY1305_OLD: 0, CHACHA20_POLY1305_TLS13: 0}
 TAG_LEN = 16
 
 REC_BAD_MAC = -1          # tls1_enc returns -1 (bad_record_mac)
@@ -497,7 +502,8 @@ def seal_wire(table: SessionTable, d_streams: int, n_streams: int, d_data: int, 
 def seal_wire_size(aead: int, data_len: int, max_fragment: int = 0, tag_len: int = 0,
                    version: int | None = None) -> int:
     """Wire bytes of one tlsgpu_seal_wire stream; version=0x0304: TLS 1.3 framing
-    (tlsgpu_seal_wire_size_v)."""
+    (tlsgpu_seal_wire_size_v).  CHACHA20_POLY1305_TLS13 has that framing with
+    any version and with none."""
     if version is None:
         return int(load_library().tlsgpu_seal_wire_size(aead, data_len, max_fragment, tag_len))
     return int(load_library().tlsgpu_seal_wire_size_v(aead, version, data_len, max_fragment,

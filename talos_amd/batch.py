@@ -32,7 +32,9 @@ class RecordBatch:
     ``tls13=True``: the entries belong to a TLS 1.3 session table
     (include/tlsgpu.h): no explicit nonce, a seal's output is content + inner
     type + tag (``content_type`` is the inner type) and an open's the whole
-    inner plaintext, fragment - tag.  The default is the TLS 1.2 layout.
+    inner plaintext, fragment - tag; the entries' kinds may be the TLS 1.3
+    AES-GCM kinds and CHACHA20_POLY1305_TLS13, mixed.  The default is the
+    TLS 1.2 layout.
     """
 
     def __init__(self, engine, entries, mode: str, in_shift: int = 0, out_shift: int = 0,

@@ -283,12 +283,25 @@ __device__ __forceinline__ void cc_block_sk(uint32_t x[16], cu32c* k, uint32_t c
 // The staged loop and the record's end.  NARROW (round 5): every record's
 // offset in its buffer fits 32 bits, so a piece's pointer is one ds_bpermute
 // of that offset (plus the buffer base) instead of two of the 64-bit pointer.
-template <bool SEAL, bool LATE_STORES, bool NARROW, bool UKEY = false>
+// T13: the TLS 1.3 record layout (RFC 8446 5.2; TLSGPU_CHACHA20_POLY1305_TLS13),
+// compile-time because this kernel sits at 4 waves per SIMD with no register
+// room.  n is the inner plaintext, content || type.  Seal: the
+// source holds n - 1 bytes, so the gather's load predicate runs over n - 1 and
+// everything else over n; the piece that holds offset n - 1 drops what was
+// loaded at and after it and takes the type byte, which comes from the
+// descriptor's type bits (d_in is never read for it), before the XOR with the
+// key stream.  When n - 1 is a multiple of 16, 64 or 128 the type byte is alone
+// in a new piece, block or step, and that step's gather loads nothing for the
+// record.  A step that does not hold the type byte pays one compare.
+template <bool SEAL, bool LATE_STORES, bool NARROW, bool UKEY = false, bool T13 = false>
 __device__ __forceinline__ void cc_tls_body(const BatchArgs& a, uint32_t r, uint32_t lane, uint8_t* tile,
                                             uint8_t* key, cu32c* ukey, bool active, uint32_t n,
-                                            uint32_t tag_len,
+                                            uint32_t tag_len_or_type,
                                             uint32_t c13, uint32_t c14, uint32_t c15,
                                             uint64_t src_v, uint64_t dst_v, Poly& p) {
+  // T13: the tag is 16 bytes, and the register that carries a TLS 1.2 record's
+  // tag length carries a seal's inner content type instead (none to spare)
+  const uint32_t tag_len = T13 ? 16u : tag_len_or_type;
   // src_v / dst_v: the record's pointers, or with NARROW its 32-bit offsets in
   // the caller's buffers (an active record lies inside them, each at most
   // 4 GiB; an inactive lane's value is never used: its length shuffles as 0)
@@ -310,7 +323,8 @@ __device__ __forceinline__ void cc_tls_body(const BatchArgs& a, uint32_t r, uint
     for (int k = 0; k < kCcP; k++) {
       const uint32_t rr = kCcR * k + lane / kCcP;
       const uint32_t off = base + 16u * (((lane % kCcP) - (rr >> 1)) & 7u);
-      const uint32_t snk = __shfl(n, (int)rr);
+      uint32_t snk = __shfl(n, (int)rr);
+      if (T13 && SEAL) snk -= min(snk, 1u);  // the source: the content (an active n >= 1)
       // ds_bpermute outside the branch: an inactive source lane reads as 0
       const uint64_t srck = ptr_of(src_v, a.in, rr);
       v[k] = make_uint4(0, 0, 0, 0);
@@ -350,6 +364,15 @@ __device__ __forceinline__ void cc_tls_body(const BatchArgs& a, uint32_t r, uint
       if (s + 1 < steps) gather(base + kCcStep, pf);
     }
     lds_wave_sync();
+    // T13 seal, the step that holds offset n - 1: the type byte goes into the
+    // lane's own row ahead of the blocks (no key stream is live here, so the
+    // loop below and its register peak are the TLS 1.2 ones).  One byte store:
+    // what the gather left at and after offset n - 1 of that piece lies at or
+    // past n and is masked below as in every last piece
+    if (T13 && SEAL && base < n && n - base <= kCcStep) {
+      const uint32_t tb = n - 1 - base;  // 0..127
+      tile[cc_slot(lane, tb >> 4) + (tb & 15u)] = (uint8_t)tag_len_or_type;  // the lane's own row
+    }
     // en/decrypt + MAC this lane's row: 2 ChaCha blocks
     if (base < n && !(a.hy_flags & kCcDiagNoCompute)) {
 #pragma unroll 1
@@ -427,7 +450,7 @@ __device__ __forceinline__ void cc_tls_body(const BatchArgs& a, uint32_t r, uint
   if (!active) return;
   const uint8_t* src = NARROW ? a.in + (uint32_t)src_v : (const uint8_t*)(uintptr_t)src_v;
   uint8_t* dst = NARROW ? a.out + (uint32_t)dst_v : (uint8_t*)(uintptr_t)dst_v;
-  poly_block(p, 13u, 0, n, 0, 1u << 24);  // le64(ad_len) || le64(ct_len)
+  poly_block(p, T13 ? 5u : 13u, 0, n, 0, 1u << 24);  // le64(ad_len) || le64(ct_len)
   uint32_t mac[4];
   poly_finish(p, mac);
   int32_t* slot = a.status + r;
@@ -461,13 +484,17 @@ __device__ __forceinline__ void cc_tls_body(const BatchArgs& a, uint32_t r, uint
   }
 }
 
-template <bool SEAL, bool LATE_STORES, bool NARROW = false>
+// T13: records of TLSGPU_CHACHA20_POLY1305_TLS13 sessions only, in the TLS 1.3
+// layout (cc_tls_body); n = len + 1 on seal, len - 16 on open (the unpad pass
+// turns the open's status n into the content length afterwards).
+template <bool SEAL, bool LATE_STORES, bool NARROW = false, bool T13 = false>
 __device__ void cc_tls_wave(const BatchArgs& a, uint32_t r, uint32_t lane, uint8_t* tile,
                             uint8_t* keys) {
   // --- parse (the fields the end of the record needs are re-derived there)
   bool active = false;
   uint32_t n = 0, tag_len = 16, c13 = 0, c14 = 0, c15 = 0;
-  uint32_t ad2 = 0;  // AD word 2 (type, version, length high byte); words 0-1 = c14/c15 (RFC)
+  uint32_t ad2 = 0;  // AD word 2 (type, version, length high byte); words 0-1 = c14/c15 (RFC);
+                     // unused by T13, whose AD is the record header
   const uint8_t* src = nullptr;
   uint8_t* dst = nullptr;
   uint32_t sq_hi = 0, sq_lo = 0;
@@ -485,12 +512,16 @@ __device__ void cc_tls_wave(const BatchArgs& a, uint32_t r, uint32_t lane, uint8
       if (a.fused) {
         const uint64_t len = d.len_type & 0xFFFFFFu, tag = S->tag_len;
         const uint64_t eiv = S->nonce_in_record ? 8u : 0u;
-        const uint64_t out_len = SEAL ? len + eiv + tag : (len >= eiv + tag ? len - eiv - tag : 0);
+        // a TLS 1.3 seal writes content || type || tag (check_record_bounds's spans)
+        const uint64_t extra = T13 && kind == TLSGPU_CHACHA20_POLY1305_TLS13 ? 1u : 0u;
+        const uint64_t out_len =
+            SEAL ? len + eiv + extra + tag : (len >= eiv + tag ? len - eiv - tag : 0);
         in_bounds = !(d.in_off > a.in_bytes || len > a.in_bytes - d.in_off ||
                       d.out_off > a.out_bytes || out_len > a.out_bytes - d.out_off);
         if (!in_bounds) st0 = TLSGPU_REC_OUT_OF_BOUNDS;
       }
-      if (kind == TLSGPU_CHACHA20_POLY1305 && in_bounds) {  // the draft ("old") suite: chacha_batch_kernel
+      // this kernel's suite (the draft ("old") suite: chacha_batch_kernel)
+      if (kind == (T13 ? TLSGPU_CHACHA20_POLY1305_TLS13 : TLSGPU_CHACHA20_POLY1305) && in_bounds) {
         tag_len = S->tag_len;
         const uint32_t len = d.len_type & 0xFFFFFFu, type = d.len_type >> 24;
         if (!SEAL && len < tag_len) {  // t1_enc.c:958-959 (no explicit nonce for ChaCha)
@@ -498,7 +529,8 @@ __device__ void cc_tls_wave(const BatchArgs& a, uint32_t r, uint32_t lane, uint8
         } else {
           active = true;
           sess = d.session;
-          n = SEAL ? len : len - tag_len;
+          n = SEAL ? len + (T13 ? 1u : 0u) : len - tag_len;
+          if (T13) tag_len = type;  // cc_tls_body: the tag is 16 bytes, this is the type
           src = a.in + d.in_off;
           dst = a.out + d.out_off;
           // nonce: RFC 7905 fixed(12) XOR (0^4 || seq)
@@ -525,7 +557,11 @@ __device__ void cc_tls_wave(const BatchArgs& a, uint32_t r, uint32_t lane, uint8
     uint32_t ks[16];
     cc_block_lds(ks, key, 0u, c13, c14, c15);  // counter 0 block -> one-time Poly1305 key
     poly_init(p, ks);
-    poly_block(p, sq_hi, sq_lo, ad2, n & 0xFF, 1u << 24);  // 13-B AD, pad16
+    if (T13)  // the record header 17 03 03 BE16(ciphertext with the tag), pad16
+      poly_block(p, 0x17u | (3u << 8) | (3u << 16) | (((n + 16u) >> 8) << 24), (n + 16u) & 0xFF, 0, 0,
+                 1u << 24);
+    else
+      poly_block(p, sq_hi, sq_lo, ad2, n & 0xFF, 1u << 24);  // 13-B AD, pad16
   }
   // NARROW (the launch's choice, launch_chacha): a fused batch whose buffers
   // are at most 4 GiB each, so a record's offset fits 32 bits
@@ -540,11 +576,11 @@ __device__ void cc_tls_wave(const BatchArgs& a, uint32_t r, uint32_t lane, uint8
                     !(a.hy_flags & kCcNoUkey);
   if (ukey) {
     cu32c* k = (cu32c*)(const uint32_t*)a.sessions[sid0].chacha_key;
-    cc_tls_body<SEAL, LATE_STORES, NARROW, true>(a, r, lane, tile, key, k, active, n, tag_len, c13,
-                                                 c14, c15, sv, dv, p);
+    cc_tls_body<SEAL, LATE_STORES, NARROW, true, T13>(a, r, lane, tile, key, k, active, n, tag_len,
+                                                      c13, c14, c15, sv, dv, p);
   } else {
-    cc_tls_body<SEAL, LATE_STORES, NARROW, false>(a, r, lane, tile, key, nullptr, active, n,
-                                                  tag_len, c13, c14, c15, sv, dv, p);
+    cc_tls_body<SEAL, LATE_STORES, NARROW, false, T13>(a, r, lane, tile, key, nullptr, active, n,
+                                                       tag_len, c13, c14, c15, sv, dv, p);
   }
 }
 
@@ -653,23 +689,25 @@ __device__ __forceinline__ void cc_parse_raw(const RawJob& j, const DevSession* 
 }
 
 // TLS batches: LDS-staged coalesced data path (cc_tls_wave), 4 waves per SIMD.
-template <bool SEAL>
+// T13 (this kernel and chacha_tls_kernel): the instantiation a TLS 1.3 table runs.
+template <bool SEAL, bool T13 = false>
 __global__ __launch_bounds__(kCcThreads) void chacha_tls_wide_kernel(BatchArgs a) {
   __shared__ __attribute__((aligned(16))) uint8_t tiles[kCcThreads / kWave][kCcTile];
   __shared__ __attribute__((aligned(16))) uint8_t keys[kCcThreads / kWave][kCcKeys];
   const uint32_t lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  cc_tls_wave<SEAL, false>(a, blockIdx.x * blockDim.x + threadIdx.x, lane, tiles[wave], keys[wave]);
+  cc_tls_wave<SEAL, false, false, T13>(a, blockIdx.x * blockDim.x + threadIdx.x, lane, tiles[wave],
+                                       keys[wave]);
 }
 // the same with 32-bit pointer shuffles (NARROW: cc_tls_body) — what a fused
 // batch (bounds known, buffers of at most 4 GiB) runs: C +0.6 %
 // (profiles/r05ap_ab_cc_narrow.txt); 64-bit shuffles otherwise
-template <bool SEAL>
+template <bool SEAL, bool T13 = false>
 __global__ __launch_bounds__(kCcThreads) void chacha_tls_kernel(BatchArgs a) {
   __shared__ __attribute__((aligned(16))) uint8_t tiles[kCcThreads / kWave][kCcTile];
   __shared__ __attribute__((aligned(16))) uint8_t keys[kCcThreads / kWave][kCcKeys];
   const uint32_t lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  cc_tls_wave<SEAL, false, true>(a, blockIdx.x * blockDim.x + threadIdx.x, lane, tiles[wave],
-                                 keys[wave]);
+  cc_tls_wave<SEAL, false, true, T13>(a, blockIdx.x * blockDim.x + threadIdx.x, lane, tiles[wave],
+                                      keys[wave]);
 }
 // the LATE_STORES order (A/B only, TLSGPU_CC_ORDER): at 3 waves per SIMD (131
 // VGPRs), and held to 128 VGPRs (4 waves per SIMD, 5 spilled)
@@ -750,7 +788,11 @@ __global__ __launch_bounds__(kWave) void chacha_raw_wave_kernel(BatchArgs a) {
 }
 
 // TLSGPU_CHACHA_LEGACY=1 selects the per-lane data path for TLS batches too
-// (A/B measurement of the staged kernel).
+// (A/B measurement of the staged kernel).  An A/B switch for TLS 1.2 only: the
+// per-lane kernels know the TLS 1.2 layouts alone and leave the TLS records of
+// TLSGPU_CHACHA20_POLY1305_TLS13 sessions untouched (cc_parse_tls), so those
+// always take the staged kernel; a raw EVP job on such a session, which the EVP
+// surface never creates, is PUBLIC_INVALID like any kind outside 1..4.
 static bool getenv_legacy_chacha() {
   static const bool v = [] {
     const char* e = getenv("TLSGPU_CHACHA_LEGACY");
@@ -763,6 +805,25 @@ static bool getenv_legacy_chacha() {
 int launch_chacha(const BatchArgs& a, bool seal, bool raw, bool rfc, bool old, hipStream_t s) {
   if (a.n == 0) return 0;
   dim3 grid((a.n + 255) / 256), block(256);
+  if (a.tls13) {  // (never set for raw jobs)
+    // a TLS 1.3 table (one generation per table): its only ChaCha kind is the
+    // TLS 1.3 one, run by the staged kernel's T13 instantiation whatever the
+    // A/B switches say, then on open the unpad pass of the ChaCha sessions
+    // (rounds 0: no record of a GCM session is taken again)
+    if (!rfc) return 0;
+    BatchArgs b = a;
+    b.hy_flags = 0;
+    const bool narrow = a.fused && a.in_bytes <= (1ull << 32) && a.out_bytes <= (1ull << 32);
+    if (narrow) {
+      if (seal) hipLaunchKernelGGL((chacha_tls_kernel<true, true>), grid, block, 0, s, b);
+      else hipLaunchKernelGGL((chacha_tls_kernel<false, true>), grid, block, 0, s, b);
+    } else {
+      if (seal) hipLaunchKernelGGL((chacha_tls_wide_kernel<true, true>), grid, block, 0, s, b);
+      else hipLaunchKernelGGL((chacha_tls_wide_kernel<false, true>), grid, block, 0, s, b);
+    }
+    if (hipGetLastError() != hipSuccess) return -1;
+    return seal ? 0 : launch_tls13_unpad(a, 0, s);
+  }
   const bool staged = !raw && !getenv_legacy_chacha();
   if (raw && !getenv_legacy_chacha()) {  // one wave per job
     if (seal) hipLaunchKernelGGL((chacha_raw_wave_kernel<true>), dim3(a.n), dim3(kWave), 0, s, a);

@@ -155,16 +155,21 @@ extern "C" void tlsgpu_sessions_destroy(tlsgpu_sessions* t) {
 bool tg::valid_params(const tlsgpu_session_params& p) {
   uint32_t tag = p.tag_len == 0 ? 16 : p.tag_len;
   if (tag > 16 || p.fixed_iv_len > 12) return false;
-  // TLS 1.3 (RFC 8446 section 5.3): AES-GCM only, the whole 12-byte write IV, a 16-byte tag
+  // TLS 1.3 (RFC 8446 section 5.3): AES-GCM or the TLS 1.3 ChaCha kind (the TLS 1.2
+  // ChaCha kinds name TLS 1.2 record layouts), the whole 12-byte write IV, a 16-byte tag
   if (p.version == kTls13Version &&
       (p.fixed_iv_len != 12 || tag != 16 ||
-       (p.aead != TLSGPU_AES_128_GCM && p.aead != TLSGPU_AES_256_GCM)))
+       (p.aead != TLSGPU_AES_128_GCM && p.aead != TLSGPU_AES_256_GCM &&
+        p.aead != TLSGPU_CHACHA20_POLY1305_TLS13)))
     return false;
+  // ... and that kind exists in TLS 1.3 only
+  if (p.aead == TLSGPU_CHACHA20_POLY1305_TLS13 && p.version != kTls13Version) return false;
   switch (p.aead) {
     case TLSGPU_AES_128_GCM: return p.key_len == 16;
     case TLSGPU_AES_256_GCM:
     case TLSGPU_CHACHA20_POLY1305:
-    case TLSGPU_CHACHA20_POLY1305_OLD: return p.key_len == 32;
+    case TLSGPU_CHACHA20_POLY1305_OLD:
+    case TLSGPU_CHACHA20_POLY1305_TLS13: return p.key_len == 32;
   }
   return false;
 }
@@ -406,8 +411,8 @@ int tg::run_batch(tlsgpu_sessions* t, const void* d_descs, uint32_t n, const uin
                   uint8_t* d_out, int32_t* d_status, hipStream_t s, bool seal, bool raw,
                   const Bounds* bounds, unsigned kinds, unsigned hints, tlsgpu_record* type_out) {
   if (hints == ~0u) hints = t->hints.load(std::memory_order_relaxed);
-  bool have[5];
-  for (int k = 0; k < 5; k++) have[k] = t->have[k] && ((kinds >> k) & 1u);
+  bool have[kKinds];
+  for (int k = 0; k < kKinds; k++) have[k] = t->have[k] && ((kinds >> k) & 1u);
   BatchArgs a = {};
   a.sessions = t->d_sess;
   a.gcm_tables = t->d_gcm;
@@ -466,11 +471,16 @@ int tg::run_batch(tlsgpu_sessions* t, const void* d_descs, uint32_t n, const uin
   // keeps the launch sequence with the device-side selection).
   const bool fused_gcm = g_fused && bounds && impl == TLSGPU_GCM_QUEUE && a.pws == 1 &&
                          (have[TLSGPU_AES_128_GCM] != have[TLSGPU_AES_256_GCM]) &&
-                         !have[TLSGPU_CHACHA20_POLY1305] && !have[TLSGPU_CHACHA20_POLY1305_OLD];
-  // ... and the same for a batch of RFC 7539 ChaCha sessions only: the staged
-  // ChaCha kernel checks bounds and writes the statuses of the records it does
-  // not run itself (chacha_kernels.hip cc_tls_wave)
-  const bool fused_cc = g_fused && bounds && !raw && have[TLSGPU_CHACHA20_POLY1305] &&
+                         !have[TLSGPU_CHACHA20_POLY1305] && !have[TLSGPU_CHACHA20_POLY1305_OLD] &&
+                         !have[TLSGPU_CHACHA20_POLY1305_TLS13];
+  // ... and the same for a batch of RFC 7539 ChaCha sessions only, or of a TLS 1.3
+  // table whose only kind is the TLS 1.3 ChaCha one: the staged ChaCha kernel
+  // checks bounds and writes the statuses of the records it does not run itself
+  // (chacha_kernels.hip cc_tls_wave).  have_cc: the staged kernel's suite, RFC 7905
+  // or, in a TLS 1.3 table, the TLS 1.3 kind
+  const bool have_cc = t13 ? have[TLSGPU_CHACHA20_POLY1305_TLS13] : have[TLSGPU_CHACHA20_POLY1305];
+  const bool fused_cc = g_fused && bounds && !raw && have_cc &&
+                        !have[t13 ? TLSGPU_CHACHA20_POLY1305 : TLSGPU_CHACHA20_POLY1305_TLS13] &&
                         !have[TLSGPU_CHACHA20_POLY1305_OLD] && !have[TLSGPU_AES_128_GCM] &&
                         !have[TLSGPU_AES_256_GCM];
   const bool fused = fused_gcm || fused_cc;
@@ -580,9 +590,9 @@ int tg::run_batch(tlsgpu_sessions* t, const void* d_descs, uint32_t n, const uin
                   hipGetErrorString(hipGetLastError()));
     }
   }
-  if ((have[TLSGPU_CHACHA20_POLY1305] || have[TLSGPU_CHACHA20_POLY1305_OLD]) &&
-      launch_chacha(a, seal, raw, have[TLSGPU_CHACHA20_POLY1305],
-                    have[TLSGPU_CHACHA20_POLY1305_OLD], s))
+  // (a TLS 1.3 table: launch_chacha also runs the ChaCha sessions' unpad pass after an open)
+  if ((have_cc || have[TLSGPU_CHACHA20_POLY1305_OLD]) &&
+      launch_chacha(a, seal, raw, have_cc, have[TLSGPU_CHACHA20_POLY1305_OLD], s))
     return fail(TLSGPU_EHIP, "chacha launch: %s", hipGetErrorString(hipGetLastError()));
   if (pool_scratch) HIPCHK(hipFreeAsync(pool_scratch, s));
   return TLSGPU_OK;

@@ -64,7 +64,7 @@ struct tlsgpu_sessions {
   int generation = 0;          // 0: nothing installed yet; 12 / 13: every session is TLS <= 1.2 /
                                // TLS 1.3 (version 0x0304, RFC 8446 record layout) — set by
                                // the first install, one generation per table
-  bool have[5];                // any session of kind k installed
+  bool have[tg::kKinds];       // any session of kind k installed (enum tlsgpu_aead)
   std::atomic<unsigned> hints{0};  // TLSGPU_HINT_* (tlsgpu_sessions_hint)
   // EVP contexts: per-slot event of the slot's last install or scrub, so init
   // and cleanup need not wait on the device (created on a slot's first use)

@@ -115,7 +115,8 @@ static int host_batch(tlsgpu_sessions* t, bool seal, const tlsgpu_record* h_recs
     if (r.session < t->capacity) {
       const int k = t->kinds[r.session];
       const bool gcm = k == TLSGPU_AES_128_GCM || k == TLSGPU_AES_256_GCM;
-      over = (gcm && !t13 ? 8 : 0) + (gcm && t13 && seal ? 1 : 0) + t->tag_lens[r.session];
+      const bool s13 = tls13_session((uint32_t)k, t13 ? 0u : 1u);  // GCM or ChaCha: + the type byte
+      over = (gcm && !s13 ? 8 : 0) + (s13 && seal ? 1 : 0) + t->tag_lens[r.session];
     }
     *lo = std::min<uint64_t>(r.out_off, out_bytes);
     *hi = std::min<uint64_t>(r.out_off + (seal ? len + over : (len > over ? len - over : 0)),
@@ -373,13 +374,15 @@ extern "C" uint64_t tlsgpu_seal_wire_size(int aead, uint32_t data_len, uint32_t 
   const uint32_t frag = max_fragment == 0 || max_fragment > 16384 ? 16384 : max_fragment;
   const uint64_t nrec = ((uint64_t)data_len + frag - 1) / frag;
   const uint64_t eiv = aead == TLSGPU_AES_128_GCM || aead == TLSGPU_AES_256_GCM ? 8 : 0;
+  // the TLS 1.3 ChaCha kind: header || content || inner type || tag(16), whatever the version
+  if (aead == TLSGPU_CHACHA20_POLY1305_TLS13) return data_len + nrec * (5 + 1 + 16);
   return data_len + nrec * (5 + eiv + (tag_len ? tag_len : 16));
 }
 
 extern "C" uint64_t tlsgpu_seal_wire_size_v(int aead, uint16_t version, uint32_t data_len,
                                             uint32_t max_fragment, uint32_t tag_len) {
   const bool gcm = aead == TLSGPU_AES_128_GCM || aead == TLSGPU_AES_256_GCM;
-  if (version != kTls13Version || !gcm)
+  if (version != kTls13Version || !gcm)  // (the TLS 1.3 ChaCha kind: TLS 1.3 framing there too)
     return tlsgpu_seal_wire_size(aead, data_len, max_fragment, tag_len);
   // TLS 1.3: header(5) || content || inner type(1) || tag(16) per record, no explicit nonce
   const uint32_t frag = max_fragment == 0 || max_fragment > 16384 ? 16384 : max_fragment;

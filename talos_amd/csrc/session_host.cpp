@@ -185,16 +185,18 @@ bool host_session_image(const tlsgpu_session_params& p, DevSession* s, DevGcmTab
                         bool bitsliced_masks, bool compact) {
   memset(s, 0, sizeof(*s));
   const bool gcm = p.aead == TLSGPU_AES_128_GCM || p.aead == TLSGPU_AES_256_GCM;
-  const bool cc = p.aead == TLSGPU_CHACHA20_POLY1305 || p.aead == TLSGPU_CHACHA20_POLY1305_OLD;
+  const bool cc13 = p.aead == TLSGPU_CHACHA20_POLY1305_TLS13;  // images like kind 3, its own kind
+  const bool cc = p.aead == TLSGPU_CHACHA20_POLY1305 || p.aead == TLSGPU_CHACHA20_POLY1305_OLD || cc13;
   const uint32_t want_key = p.aead == TLSGPU_AES_128_GCM ? 16 : 32;
   const uint32_t tag = p.tag_len == 0 ? 16 : p.tag_len;
-  const bool valid = (gcm || cc) && p.key_len == want_key && tag <= 16 && p.fixed_iv_len <= 12;
+  const bool valid = (gcm || cc) && p.key_len == want_key && tag <= 16 && p.fixed_iv_len <= 12 &&
+                     (!cc13 || (p.version == 0x0304 && tag == 16 && p.fixed_iv_len == 12));
   if (!valid) return false;
   s->kind = (uint32_t)p.aead;
   s->tag_len = tag;
   s->key_len = p.key_len;
   s->fixed_nonce_len = p.fixed_iv_len;
-  s->xor_fixed_nonce = p.aead == TLSGPU_CHACHA20_POLY1305;
+  s->xor_fixed_nonce = p.aead == TLSGPU_CHACHA20_POLY1305 || cc13;
   s->nonce_in_record = gcm && p.version != 0x0304;  // TLS 1.3: no explicit nonce
   s->version = p.version;
   memcpy(s->fixed_nonce, p.fixed_iv, p.fixed_iv_len);

@@ -193,10 +193,12 @@ __device__ __forceinline__ void install_body(DevSession* __restrict__ sessions,
   reinterpret_cast<uint32_t*>(sb)[lane] = reinterpret_cast<const uint32_t*>(g_sbox.v)[lane];
   hdr[lane] = make_uint4(0, 0, 0, 0);
   const bool gcm = p.aead == TLSGPU_AES_128_GCM || p.aead == TLSGPU_AES_256_GCM;
-  const bool cc = p.aead == TLSGPU_CHACHA20_POLY1305 || p.aead == TLSGPU_CHACHA20_POLY1305_OLD;
+  const bool cc13 = p.aead == TLSGPU_CHACHA20_POLY1305_TLS13;  // installs like kind 3, its own kind
+  const bool cc = p.aead == TLSGPU_CHACHA20_POLY1305 || p.aead == TLSGPU_CHACHA20_POLY1305_OLD || cc13;
   const uint32_t want_key = p.aead == TLSGPU_AES_128_GCM ? 16 : 32;
   const uint32_t tag = p.tag_len == 0 ? 16 : p.tag_len;
-  const bool valid = (gcm || cc) && p.key_len == want_key && tag <= 16 && p.fixed_iv_len <= 12;
+  const bool valid = (gcm || cc) && p.key_len == want_key && tag <= 16 && p.fixed_iv_len <= 12 &&
+                     (!cc13 || (p.version == 0x0304 && tag == 16 && p.fixed_iv_len == 12));
   __syncthreads();
   DevSession& s = *reinterpret_cast<DevSession*>(hdr);
   uint32_t rounds = 0;
@@ -205,7 +207,7 @@ __device__ __forceinline__ void install_body(DevSession* __restrict__ sessions,
     s.tag_len = tag;
     s.key_len = p.key_len;
     s.fixed_nonce_len = p.fixed_iv_len;
-    s.xor_fixed_nonce = p.aead == TLSGPU_CHACHA20_POLY1305;
+    s.xor_fixed_nonce = p.aead == TLSGPU_CHACHA20_POLY1305 || cc13;
     s.nonce_in_record = gcm && p.version != 0x0304;  // TLS 1.3: no explicit nonce
     s.version = p.version;
     for (uint32_t k = 0; k < p.fixed_iv_len; k++) s.fixed_nonce[k] = p.fixed_iv[k];
@@ -360,8 +362,7 @@ __global__ void check_record_bounds(const tlsgpu_record* __restrict__ recs,
     const DevSession& S = sessions[r.session];
     const uint64_t eiv = S.nonce_in_record ? 8u : 0u, tag = S.tag_len;
     // a TLS 1.3 seal writes content || type || tag (RFC 8446 5.2)
-    const bool gcm = S.kind == TLSGPU_AES_128_GCM || S.kind == TLSGPU_AES_256_GCM;
-    const uint64_t extra = gcm && eiv == 0 ? 1u : 0u;
+    const uint64_t extra = tls13_session(S.kind, S.nonce_in_record) ? 1u : 0u;
     const uint64_t len = r.len_type & 0xFFFFFFu;
     const uint64_t in_len = len;
     const uint64_t out_len =
@@ -396,10 +397,12 @@ int launch_check_bounds(const tlsgpu_record* recs, tlsgpu_record* safe, uint32_t
 // One lane per record looks at the last byte, which is the type whenever the
 // sender did not pad; for the others the wave scans backwards, 64 x 16 B per
 // step, one record after the other.  Negative statuses and records of other
-// sessions are left alone.  Launched by the TLS 1.3 GCM launchers only, once
-// per AES key size after that size's kernels (`rounds`: a record is taken in
-// the pass of its own session's key size, so never twice): a TLS 1.2 batch
-// launches nothing new.  type_out != null (tlsgpu_open_wire): the record's
+// sessions are left alone.  Launched by the TLS 1.3 launchers only, once per
+// AES key size after that size's kernels and once for the ChaCha sessions after
+// theirs (`rounds`: a record is taken in the pass of its own session's AES
+// rounds, 0 for ChaCha, so never twice): a TLS 1.2 batch launches nothing new,
+// and a TLS 1.3 batch no pass for a kind its table does not hold.
+// type_out != null (tlsgpu_open_wire): the record's
 // inner content type also replaces the type bits of type_out[r].len_type.
 __global__ __launch_bounds__(256) void tls13_unpad_kernel(const tlsgpu_record* recs,  // may be type_out
                                                           uint32_t n,
@@ -423,8 +426,7 @@ __global__ __launch_bounds__(256) void tls13_unpad_kernel(const tlsgpu_record* r
     const int32_t st = status[r];
     if (d.session < n_sessions && st >= 0) {
       const DevSession& S = sessions[d.session];
-      const bool gcm = S.kind == TLSGPU_AES_128_GCM || S.kind == TLSGPU_AES_256_GCM;
-      if (gcm && S.nonce_in_record == 0 && S.rounds == rounds) {
+      if (tls13_session(S.kind, S.nonce_in_record) && S.rounds == rounds) {
         p = out + d.out_off;
         m = (uint32_t)st;
         lt = d.len_type;

@@ -22,7 +22,7 @@ struct alignas(16) DevSession {
   uint32_t tag_len;           // 1..16
   uint32_t key_len;
   uint32_t fixed_nonce_len;   // 4 / 12 / 0
-  uint32_t xor_fixed_nonce;   // ChaCha RFC 7905
+  uint32_t xor_fixed_nonce;   // ChaCha RFC 7905 (and the TLS 1.3 ChaCha kind: the same nonce)
   uint32_t nonce_in_record;   // GCM explicit nonce (TLS 1.2); 0 for a TLS 1.3 GCM session,
                               // which is how the GCM kernels tell the two apart (gcm_tls13)
   uint32_t version;           // TLS version for the AAD
@@ -35,6 +35,18 @@ struct alignas(16) DevSession {
   uint32_t reserved[112];
 };
 static_assert(sizeof(DevSession) == 1024, "DevSession layout");
+
+// "Is this session TLS 1.3?" (the RFC 8446 5.2-5.4 record layout): the ChaCha
+// kind that exists in TLS 1.3 only, or a GCM session without an explicit nonce.
+// Every kernel and host path that frames, bounds or unpads records asks here.
+// (On the host, where only the table's generation is known, nonce_in_record is
+// "the table is not TLS 1.3".)
+__host__ __device__ __forceinline__ bool tls13_session(uint32_t kind, uint32_t nonce_in_record) {
+  return kind == TLSGPU_CHACHA20_POLY1305_TLS13 ||
+         ((kind == TLSGPU_AES_128_GCM || kind == TLSGPU_AES_256_GCM) && nonce_in_record == 0);
+}
+// number of AEAD kinds + 1: arrays indexed by enum tlsgpu_aead
+constexpr int kKinds = TLSGPU_CHACHA20_POLY1305_TLS13 + 1;
 
 // Per-session GHASH tables (GCM sessions only), 16-B aligned, in HBM.
 //   basis[p]      = K * x^p, K = H^64, p = 0..127 (little-endian words); a
@@ -224,7 +236,8 @@ struct BatchArgs {
                                     // workgroup {start, end (s_memrealtime), rlo, rhi}
   uint32_t tls13;                   // the table's sessions are TLS 1.3: the GCM launchers run
                                     // the kernels compiled for that record layout (their *13
-                                    // twins) and, after an open, the unpad pass
+                                    // twins), launch_chacha the staged kernel's TLS 1.3
+                                    // instantiation, and each, after an open, the unpad pass
   tlsgpu_record* type_out;          // TLS 1.3 open, non-null (tlsgpu_open_wire: the engine's own
                                     // descriptors): the unpad pass also moves every opened
                                     // record's inner content type into len_type's type bits
@@ -301,7 +314,8 @@ int launch_gcm_pw13(const BatchArgs& a, const RecPre* pre, bool seal, int rounds
                     hipStream_t s);
 // TLS 1.3 open: inner-plaintext lengths in a.status -> content lengths, for the
 // records of sessions with `rounds` AES rounds (session_kernels.hip; called by
-// the TLS 1.3 launchers after their kernels, once per key size)
+// the TLS 1.3 launchers after their kernels, once per key size; rounds 0: the
+// ChaCha sessions, after launch_chacha's kernel)
 int launch_tls13_unpad(const BatchArgs& a, int rounds, hipStream_t s);
 int launch_gcm_stream(const DevSession* sessions, const DevGcmTables* tables, uint32_t session,
                       GcmStream* st, const GcmStreamOp* ops, uint32_t nops, hipStream_t s);
@@ -313,6 +327,8 @@ int launch_gcm_hy14(const BatchArgs& a, const RecPre* pre, bool seal, int bs_wav
                     hipStream_t s);
 int launch_bs_ecb(const DevSession* sessions, uint32_t session, int rounds, const void* d_in,
                   void* d_out, uint32_t nblocks, hipStream_t s);
+// rfc / old: the batch may hold records of the staged kernel's suite (RFC 7905,
+// or in a TLS 1.3 table TLSGPU_CHACHA20_POLY1305_TLS13) / of the draft suite
 int launch_chacha(const BatchArgs& a, bool seal, bool raw, bool rfc, bool old, hipStream_t s);
 
 // Doorbell slot of the persistent EVP server (evp_server.hip, evp_doorbell.cpp): one

@@ -209,14 +209,11 @@ __global__ __launch_bounds__(64 * kFrameWaves) void wire_frame_kernel(
   uint2* list = lists[wave];
   tlsgpu_wire_stream st = {};
   WireWalk walk = {};
-  bool t13 = false;  // the stream's session is TLS 1.3: a GCM session without an explicit nonce
+  bool t13 = false;  // the stream's session is TLS 1.3 (tls13_session)
   if (active) {
     st = streams[s];
-    if (st.session < n_sessions) {
-      const uint32_t kind = sessions[st.session].kind;
-      t13 = (kind == TLSGPU_AES_128_GCM || kind == TLSGPU_AES_256_GCM) &&
-            sessions[st.session].nonce_in_record == 0;
-    }
+    if (st.session < n_sessions)
+      t13 = tls13_session(sessions[st.session].kind, sessions[st.session].nonce_in_record);
     walk = wire_walk(st, wire + st.wire_off, 0xFFFFFFFFu, wins[wave], lane, t13,
                      [&](uint32_t i, uint32_t pos, const Hdr& h) {
                        if (lane == 0 && i < kList) list[i] = make_uint2(pos, (h.type << 24) | h.len);
@@ -417,10 +414,9 @@ __global__ __launch_bounds__(256) void wire_seal_frame_kernel(
   res.first = first;
   if (nrec) {
     const DevSession& S = sessions[st.session];
-    // TLS 1.3 (a GCM session without an explicit nonce): the fragment is content ||
-    // inner type || tag under the header 17 03 03 (RFC 8446 5.2); st.type is the inner type
-    const bool t13 = (S.kind == TLSGPU_AES_128_GCM || S.kind == TLSGPU_AES_256_GCM) &&
-                     S.nonce_in_record == 0;
+    // TLS 1.3 (tls13_session: GCM or ChaCha): the fragment is content || inner type ||
+    // tag under the header 17 03 03 (RFC 8446 5.2); st.type is the inner type
+    const bool t13 = tls13_session(S.kind, S.nonce_in_record);
     const uint32_t over = (S.nonce_in_record ? 8u : 0u) + (t13 ? 1u : 0u) + S.tag_len;  // eivlen + tag
     uint64_t pos = st.wire_off;
     for (uint32_t k = 0; k < nrec; k++) {

@@ -16,12 +16,22 @@ handshake keys do not open and are left out.
 
 The AEAD used to open the records here is the oracle's; the test suite then
 checks the helper's seal against the captured bytes, and the engine against
-both.  usage: tools/make_tls13_fixture.py [out.json]
+both.  usage: tools/make_tls13_fixture.py [--suite SUITE] [out.json]
+
+--suite TLS_CHACHA20_POLY1305_SHA256 writes tests/golden/tls13_wire_chacha.json
+in the same format with the same writes.  Python's ssl cannot choose TLS 1.3
+suites, so the tool writes a temporary OpenSSL configuration (system_default ->
+Ciphersuites = SUITE) and starts itself as a fresh child process with
+OPENSSL_CONF pointing at it; still two MemoryBIOs, no socket.  The records are
+opened with the oracle's RFC 7905 AEAD (kind 3: the TLS 1.3 suite's cipher and
+nonce are the same), key and IV from HKDF-Expand-Label with SHA-256.
 """
+import argparse
 import base64
 import json
 import os
 import ssl
+import subprocess
 import sys
 import tempfile
 
@@ -31,6 +41,10 @@ import pyoracle as po  # noqa: E402
 import tls13_helper as t13  # noqa: E402
 
 PEM = os.path.join(ROOT, "tests", "golden", "server.pem")
+GOLDEN_CHACHA = os.path.join(ROOT, "tests", "golden", "tls13_wire_chacha.json")
+# suite -> (oracle AEAD kind, hash of the key schedule); the helper's table and ChaCha
+SUITES = dict(t13.SUITES, TLS_CHACHA20_POLY1305_SHA256=(po.CHACHA20_POLY1305, "sha256"))
+CHILD_ENV = "MAKE_TLS13_FIXTURE_CHILD"   # set in the child that runs under the suite's config
 CLIENT_WRITES = [1, 16, 1008]        # small: the fixture is committed
 SERVER_WRITES = [49, 992, 16385]     # the last one goes out as two records
 
@@ -39,7 +53,28 @@ def pattern(n: int, salt: int) -> bytes:
     return bytes((7 * i + 13 * salt + (i >> 8)) & 0xFF for i in range(n))
 
 
-def main(out_path: str) -> None:
+def traffic_keys(secret: bytes, suite: str):
+    kind, hashname = SUITES[suite]
+    return (kind, t13.hkdf_expand_label(secret, "key", po.KEY_LEN[kind], hashname),
+            t13.hkdf_expand_label(secret, "iv", 12, hashname))
+
+
+def run_with_suite(suite: str, out_path: str) -> None:
+    """This tool again, in a fresh process whose OpenSSL offers `suite` alone."""
+    conf = tempfile.NamedTemporaryFile("w", suffix=".cnf", delete=False)
+    conf.write("openssl_conf = openssl_init\n[openssl_init]\nssl_conf = ssl_sect\n"
+               "[ssl_sect]\nsystem_default = system_default_sect\n"
+               "[system_default_sect]\nCiphersuites = %s\n" % suite)
+    conf.close()
+    try:
+        env = dict(os.environ, OPENSSL_CONF=conf.name, **{CHILD_ENV: "1"})
+        subprocess.run([sys.executable, os.path.abspath(__file__), "--suite", suite, out_path],
+                       check=True, env=env)
+    finally:
+        os.unlink(conf.name)
+
+
+def main(out_path: str, want_suite: str = None) -> None:
     keylog = tempfile.NamedTemporaryFile(suffix=".keylog", delete=False)
     keylog.close()
     sctx = ssl.SSLContext(ssl.PROTOCOL_TLS_SERVER)
@@ -81,6 +116,7 @@ def main(out_path: str) -> None:
             break
     assert all(done) and cli.version() == "TLSv1.3", cli.version()
     suite = cli.cipher()[0]
+    assert want_suite in (None, suite), (want_suite, suite)
     writes = {"client": [], "server": []}
     for name, side, peer, lens in (("client", cli, srv, CLIENT_WRITES),
                                    ("server", srv, cli, SERVER_WRITES)):
@@ -105,7 +141,7 @@ def main(out_path: str) -> None:
     orc = po.Oracle()
     fixture = {"suite": suite, "openssl": ssl.OPENSSL_VERSION, "directions": []}
     for name, label in (("client", "CLIENT_TRAFFIC_SECRET_0"), ("server", "SERVER_TRAFFIC_SECRET_0")):
-        kind, key, iv = t13.traffic_keys(secrets[label], suite)
+        kind, key, iv = traffic_keys(secrets[label], suite)
         ctx = orc.aead(kind, key)
         seq, recs = 0, []
         for hdr, frag in t13.split_records(wire[name]):
@@ -135,4 +171,16 @@ def main(out_path: str) -> None:
 
 
 if __name__ == "__main__":
-    main(sys.argv[1] if len(sys.argv) > 1 else t13.GOLDEN)
+    ap = argparse.ArgumentParser(description=__doc__.split("\n")[0])
+    ap.add_argument("--suite", choices=sorted(SUITES),
+                    help="negotiate this TLS 1.3 suite (default: OpenSSL's own choice)")
+    ap.add_argument("out", nargs="?")
+    args = ap.parse_args()
+    if args.suite is None:
+        main(args.out or t13.GOLDEN)
+    else:
+        out = args.out or (GOLDEN_CHACHA if "CHACHA" in args.suite else t13.GOLDEN)
+        if os.environ.get(CHILD_ENV):
+            main(out, args.suite)
+        else:
+            run_with_suite(args.suite, out)
