@@ -16,6 +16,7 @@
 // per-record key r, so a lane owns the whole chain (no cross-lane combine);
 // the VALU does ARX + 32x32->64 multiplies only, no LDS.
 #include "chacha_wave.h"
+#include "env_knobs.h"
 
 namespace tg {
 
@@ -501,7 +502,7 @@ __device__ void cc_tls_wave(const BatchArgs& a, uint32_t r, uint32_t lane, uint8
   uint32_t sess = 0xFFFFFFFFu;
   if (r < a.n) {
     const tlsgpu_record d = reinterpret_cast<const tlsgpu_record*>(a.descs)[r];
-    // fused (round 5, engine.cpp run_batch: a batch of RFC ChaCha sessions
+    // fused (round 5, batch.cpp run_batch: a batch of RFC ChaCha sessions
     // only): the caller's descriptors, checked here by check_record_bounds's
     // rule, and the initial status of a record this kernel does not run
     int32_t st0 = TLSGPU_REC_PUBLIC_INVALID;
@@ -787,24 +788,45 @@ __global__ __launch_bounds__(kWave) void chacha_raw_wave_kernel(BatchArgs a) {
   }
 }
 
-// TLSGPU_CHACHA_LEGACY=1 selects the per-lane data path for TLS batches too
-// (A/B measurement of the staged kernel).  An A/B switch for TLS 1.2 only: the
-// per-lane kernels know the TLS 1.2 layouts alone and leave the TLS records of
-// TLSGPU_CHACHA20_POLY1305_TLS13 sessions untouched (cc_parse_tls), so those
-// always take the staged kernel; a raw EVP job on such a session, which the EVP
-// surface never creates, is PUBLIC_INVALID like any kind outside 1..4.
-static bool getenv_legacy_chacha() {
-  static const bool v = [] {
-    const char* e = getenv("TLSGPU_CHACHA_LEGACY");
-    return e && *e && *e != '0';
-  }();
-  return v;
-}
+// launch_chacha's A/B switches, read once.
+struct ChachaKnobs {
+  // TLSGPU_CHACHA_LEGACY=1 selects the per-lane data path for TLS batches too
+  // (A/B measurement of the staged kernel).  An A/B switch for TLS 1.2 only: the
+  // per-lane kernels know the TLS 1.2 layouts alone and leave the TLS records of
+  // TLSGPU_CHACHA20_POLY1305_TLS13 sessions untouched (cc_parse_tls), so those
+  // always take the staged kernel; a raw EVP job on such a session, which the EVP
+  // surface never creates, is PUBLIC_INVALID like any kind outside 1..4.
+  bool legacy = env_on("TLSGPU_CHACHA_LEGACY");
+  // TLSGPU_CC_LDS_PAD=<bytes> (A/B only): unused dynamic LDS per 4-wave
+  // workgroup, which lowers the waves per SIMD (40 KiB static: 1 B more = 3);
+  // per direction when it is 0: TLSGPU_CC_LDS_PAD_OPEN / _SEAL
+  unsigned pad_all = (unsigned)env_uint("TLSGPU_CC_LDS_PAD", 0, 10);
+  unsigned pad_dir[2] = {(unsigned)env_uint("TLSGPU_CC_LDS_PAD_OPEN", 0, 10),
+                         (unsigned)env_uint("TLSGPU_CC_LDS_PAD_SEAL", 0, 10)};
+  // the staged kernel's hy_flags: TLSGPU_CC_DIAG (bits 0-2), TLSGPU_CC_UKEY=0
+  uint32_t diag = (uint32_t)env_uint("TLSGPU_CC_DIAG", 0, 0) & 7u;
+  uint32_t no_ukey = env_not_off("TLSGPU_CC_UKEY") ? 0u : kCcNoUkey;
+  // TLSGPU_CC_NARROW=0: never the 32-bit-offset kernel
+  uint32_t no_narrow = env_not_off("TLSGPU_CC_NARROW") ? 0u : kCcNoNarrow;
+  // TLSGPU_CC_ORDER (A/B): 0 (default) tile fill after the stores, 1
+  // LATE_STORES (131 VGPRs, 3 waves per SIMD), 2 LATE_STORES held to 4 waves
+  // per SIMD (5 spilled VGPRs).  2 measured +0.6 % on C in the clock dip of
+  // the old bench order, then -0.9 % with the warm-start bench
+  // (profiles/r05w_ab_cc_order.txt, r05am_ab_warm.txt)
+  int order = (int)env_uint("TLSGPU_CC_ORDER", 0, 10);
+};
 
 // rfc / old: the batch may hold records of the RFC 7905 / draft suite.
 int launch_chacha(const BatchArgs& a, bool seal, bool raw, bool rfc, bool old, hipStream_t s) {
+  static const ChachaKnobs k{};
   if (a.n == 0) return 0;
   dim3 grid((a.n + 255) / 256), block(256);
+  // the instantiation of a kernel template for this batch's direction
+#define CC_DIR(kernel, ...) (seal ? kernel<true, ##__VA_ARGS__> : kernel<false, ##__VA_ARGS__>)
+  // NARROW needs the buffer sizes (a fused batch: run_batch passes them, and
+  // the kernel runs only records inside them): a piece's pointer is then the
+  // buffer base + a 32-bit offset
+  const bool narrow_ok = a.fused && a.in_bytes <= (1ull << 32) && a.out_bytes <= (1ull << 32);
   if (a.tls13) {  // (never set for raw jobs)
     // a TLS 1.3 table (one generation per table): its only ChaCha kind is the
     // TLS 1.3 one, run by the staged kernel's T13 instantiation whatever the
@@ -813,95 +835,33 @@ int launch_chacha(const BatchArgs& a, bool seal, bool raw, bool rfc, bool old, h
     if (!rfc) return 0;
     BatchArgs b = a;
     b.hy_flags = 0;
-    const bool narrow = a.fused && a.in_bytes <= (1ull << 32) && a.out_bytes <= (1ull << 32);
-    if (narrow) {
-      if (seal) hipLaunchKernelGGL((chacha_tls_kernel<true, true>), grid, block, 0, s, b);
-      else hipLaunchKernelGGL((chacha_tls_kernel<false, true>), grid, block, 0, s, b);
-    } else {
-      if (seal) hipLaunchKernelGGL((chacha_tls_wide_kernel<true, true>), grid, block, 0, s, b);
-      else hipLaunchKernelGGL((chacha_tls_wide_kernel<false, true>), grid, block, 0, s, b);
-    }
+    if (narrow_ok) hipLaunchKernelGGL(CC_DIR(chacha_tls_kernel, true), grid, block, 0, s, b);
+    else hipLaunchKernelGGL(CC_DIR(chacha_tls_wide_kernel, true), grid, block, 0, s, b);
     if (hipGetLastError() != hipSuccess) return -1;
     return seal ? 0 : launch_tls13_unpad(a, 0, s);
   }
-  const bool staged = !raw && !getenv_legacy_chacha();
-  if (raw && !getenv_legacy_chacha()) {  // one wave per job
-    if (seal) hipLaunchKernelGGL((chacha_raw_wave_kernel<true>), dim3(a.n), dim3(kWave), 0, s, a);
-    else hipLaunchKernelGGL((chacha_raw_wave_kernel<false>), dim3(a.n), dim3(kWave), 0, s, a);
+  if (raw && !k.legacy) {  // one wave per job
+    hipLaunchKernelGGL(CC_DIR(chacha_raw_wave_kernel), dim3(a.n), dim3(kWave), 0, s, a);
     return hipGetLastError() == hipSuccess ? 0 : -1;
   }
-  if (raw || !staged) {
-    if (seal) {
-      if (raw) hipLaunchKernelGGL((chacha_batch_kernel<true, true>), grid, block, 0, s, a);
-      else hipLaunchKernelGGL((chacha_batch_kernel<true, false>), grid, block, 0, s, a);
-    } else {
-      if (raw) hipLaunchKernelGGL((chacha_batch_kernel<false, true>), grid, block, 0, s, a);
-      else hipLaunchKernelGGL((chacha_batch_kernel<false, false>), grid, block, 0, s, a);
-    }
+  if (k.legacy) {  // the per-lane kernel, every suite
+    const auto kernel =
+        seal ? (raw ? chacha_batch_kernel<true, true> : chacha_batch_kernel<true, false>)
+             : (raw ? chacha_batch_kernel<false, true> : chacha_batch_kernel<false, false>);
+    hipLaunchKernelGGL(kernel, grid, block, 0, s, a);
     return hipGetLastError() == hipSuccess ? 0 : -1;
   }
   if (rfc) {
-    // TLSGPU_CC_LDS_PAD=<bytes> (A/B only): unused dynamic LDS per 4-wave
-    // workgroup, which lowers the waves per SIMD (40 KiB static: 1 B more = 3)
-    static const unsigned pad_all = [] {
-      const char* e = getenv("TLSGPU_CC_LDS_PAD");
-      return e ? (unsigned)strtoul(e, nullptr, 10) : 0u;
-    }();
-    // per direction (A/B): TLSGPU_CC_LDS_PAD_OPEN / _SEAL
-    static const unsigned pad_dir[2] = {[] {
-      const char* e = getenv("TLSGPU_CC_LDS_PAD_OPEN");
-      return e ? (unsigned)strtoul(e, nullptr, 10) : 0u;
-    }(), [] {
-      const char* e = getenv("TLSGPU_CC_LDS_PAD_SEAL");
-      return e ? (unsigned)strtoul(e, nullptr, 10) : 0u;
-    }()};
-    const unsigned pad = pad_all ? pad_all : pad_dir[seal ? 1 : 0];
-    static const uint32_t diag = [] {
-      const char* e = getenv("TLSGPU_CC_DIAG");
-      return e ? (uint32_t)strtoul(e, nullptr, 0) & 7u : 0u;
-    }();
-    static const uint32_t no_narrow = [] {
-      const char* e = getenv("TLSGPU_CC_NARROW");
-      return e && *e == '0' ? kCcNoNarrow : 0u;
-    }();
-    static const uint32_t no_ukey = [] {
-      const char* e = getenv("TLSGPU_CC_UKEY");
-      return e && *e == '0' ? kCcNoUkey : 0u;
-    }();
+    const unsigned pad = k.pad_all ? k.pad_all : k.pad_dir[seal ? 1 : 0];
     BatchArgs b = a;
-    b.hy_flags = diag | no_ukey;
-    // NARROW needs the buffer sizes (a fused batch: run_batch passes them, and
-    // the kernel runs only records inside them): a piece's pointer is then the
-    // buffer base + a 32-bit offset
-    const bool narrow = !no_narrow && a.fused && a.in_bytes <= (1ull << 32) &&
-                        a.out_bytes <= (1ull << 32);
-    // TLSGPU_CC_ORDER (A/B): 0 (default) tile fill after the stores, 1
-    // LATE_STORES (131 VGPRs, 3 waves per SIMD), 2 LATE_STORES held to 4 waves
-    // per SIMD (5 spilled VGPRs).  2 measured +0.6 % on C in the clock dip of
-    // the old bench order, then -0.9 % with the warm-start bench
-    // (profiles/r05w_ab_cc_order.txt, r05am_ab_warm.txt)
-    static const int order = [] {
-      const char* e = getenv("TLSGPU_CC_ORDER");
-      return e ? atoi(e) : 0;
-    }();
-    if (order == 1) {
-      if (seal) hipLaunchKernelGGL((chacha_tls_late3_kernel<true>), grid, block, pad, s, b);
-      else hipLaunchKernelGGL((chacha_tls_late3_kernel<false>), grid, block, pad, s, b);
-    } else if (order == 2) {
-      if (seal) hipLaunchKernelGGL((chacha_tls_late4_kernel<true>), grid, block, pad, s, b);
-      else hipLaunchKernelGGL((chacha_tls_late4_kernel<false>), grid, block, pad, s, b);
-    } else if (narrow) {
-      if (seal) hipLaunchKernelGGL((chacha_tls_kernel<true>), grid, block, pad, s, b);
-      else hipLaunchKernelGGL((chacha_tls_kernel<false>), grid, block, pad, s, b);
-    } else {
-      if (seal) hipLaunchKernelGGL((chacha_tls_wide_kernel<true>), grid, block, pad, s, b);
-      else hipLaunchKernelGGL((chacha_tls_wide_kernel<false>), grid, block, pad, s, b);
-    }
+    b.hy_flags = k.diag | k.no_ukey;
+    if (k.order == 1) hipLaunchKernelGGL(CC_DIR(chacha_tls_late3_kernel), grid, block, pad, s, b);
+    else if (k.order == 2) hipLaunchKernelGGL(CC_DIR(chacha_tls_late4_kernel), grid, block, pad, s, b);
+    else if (narrow_ok && !k.no_narrow) hipLaunchKernelGGL(CC_DIR(chacha_tls_kernel), grid, block, pad, s, b);
+    else hipLaunchKernelGGL(CC_DIR(chacha_tls_wide_kernel), grid, block, pad, s, b);
   }
-  if (old) {
-    if (seal) hipLaunchKernelGGL((chacha_batch_kernel<true, false, true>), grid, block, 0, s, a);
-    else hipLaunchKernelGGL((chacha_batch_kernel<false, false, true>), grid, block, 0, s, a);
-  }
+  if (old) hipLaunchKernelGGL(CC_DIR(chacha_batch_kernel, false, true), grid, block, 0, s, a);
+#undef CC_DIR
   return hipGetLastError() == hipSuccess ? 0 : -1;
 }
 

@@ -661,7 +661,7 @@ __device__ __forceinline__ RecPre rec_pre(const uint32_t j0[4], RK rk, T0F T0, T
 // kernel will run, into `pre`.  The T-tables are already in LDS (fill_aes_lds:
 // row x = 32 bank copies of Te0[x], then 32 of Te1[x]).  Only used when this
 // kernel is the batch's only one (one AES key size installed, no ChaCha, no
-// pack / per-wave-session variants: engine.cpp run_batch), so every status
+// pack / per-wave-session variants: batch.cpp run_batch), so every status
 // write here precedes this workgroup's own final one (barrier below).
 // `nrec` records, the L-th of them record map(L) (one range, or the
 // workgroup's whole pieces: one pass over all of them).
@@ -888,7 +888,7 @@ __global__ __launch_bounds__(NT, 1) void TG_GEN(gcm_hy_kernel)(BatchArgs a,
   uint32_t rlo = 0, rhi = 0;
   if (BSW == 0 && B16W == 0 && a.fused) {
     __syncthreads();  // the T-tables
-    if (a.cut_work) {  // work-balanced ranges (engine.cpp run_batch)
+    if (a.cut_work) {  // work-balanced ranges (batch.cpp run_batch)
       rlo = work_cut<NT>(a, blockIdx.x);
       rhi = work_cut<NT>(a, blockIdx.x + 1);
       fused_prologue<SEAL, ROUNDS, NT>(a, const_cast<RecPre*>(pre), rlo, rhi);

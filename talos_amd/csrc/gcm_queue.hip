@@ -29,7 +29,7 @@ int TG_GEN(launch_gcm_prep)(const BatchArgs& a, RecPre* pre, bool seal, int roun
 }
 
 #if !TG_TLS13
-// Work-balanced ranges (round 5, engine.cpp run_batch): the work
+// Work-balanced ranges (round 5, batch.cpp run_batch): the work
 // (cut_work_of) of each count range [g * rpg, (g + 1) * rpg), one workgroup
 // per range; the queue kernel's prologue cuts the batch at equal work from
 // these sums (work_cut, gcm_hybrid.h).  Reads 4 bytes of each 32-byte
@@ -54,7 +54,7 @@ int launch_range_work(const BatchArgs& a, int groups, unsigned long long* out, h
   return hipGetLastError() == hipSuccess ? 0 : -1;
 }
 
-// Whole-piece balance (round 5, engine.cpp run_batch `pieces`).  A piece is
+// Whole-piece balance (round 5, batch.cpp run_batch `pieces`).  A piece is
 // a session run inside one count range [g * rpg, (g + 1) * rpg): the unit the
 // queue kernel already processes without splitting anything.  piece_scan
 // finds each range's pieces and their work (cut_work_of); piece_sort sorts all
@@ -197,7 +197,7 @@ int TG_GEN(launch_gcm_queue)(const BatchArgs& a, const RecPre* pre, bool seal, i
   } else
 #endif
   if (a.fused && a.pack) {
-    // fused (engine.cpp run_batch): only the pack variant runs, with its own prologue
+    // fused (batch.cpp run_batch): only the pack variant runs, with its own prologue
   } else if (rounds == 10) {
     if (seal) hipLaunchKernelGGL((TG_GEN(gcm_hy_kernel)<true, 10, 1024, 0, TG_QUEUE_NB>), g, b, 0, s, a, pre);
     else hipLaunchKernelGGL((TG_GEN(gcm_hy_kernel)<false, 10, 1024, 0, TG_QUEUE_NB>), g, b, 0, s, a, pre);

@@ -1,5 +1,6 @@
 // host_internal.h — what the host units share: error reporting, the engine and
-// session-table objects, run_batch, the env helpers.  Never included by a .hip.
+// session-table objects, run_batch, the env helpers (env_knobs.h).  Never
+// included by a .hip.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -15,6 +16,7 @@
 
 #include "../../include/tlsgpu.h"
 #include "../../include/tlsgpu_evp.h"
+#include "env_knobs.h"
 #include "tlsgpu_internal.h"
 
 // Per-stream scratch for the per-record constants (RecPre) of the queue
@@ -95,7 +97,7 @@ int fail(int code, const char* fmt, ...);
 constexpr uint16_t kTls13Version = 0x0304;
 bool valid_params(const tlsgpu_session_params& p);
 
-// engine.cpp.  `kinds`: bit k set = the batch may hold records of AEAD kind k
+// batch.cpp.  `kinds`: bit k set = the batch may hold records of AEAD kind k
 // (a kernel is launched only for kinds that are installed AND in the mask; the
 // EVP queue passes the kinds its jobs use).  type_out: the descriptors again,
 // writable, when a TLS 1.3 open shall leave each record's inner content type in
@@ -109,17 +111,6 @@ inline uint64_t mono_ns() {
   return (uint64_t)std::chrono::duration_cast<std::chrono::nanoseconds>(
              std::chrono::steady_clock::now().time_since_epoch())
       .count();
-}
-
-// Environment knobs.  env_on: set and not starting with '0' (unset, empty and
-// "0" are off).  env_not_off: anything but a value starting with '0' (unset
-// and empty are on).  env_uint: strtoull in `base` of a set, non-empty value,
-// else `dflt`.
-inline bool env_on(const char* name) { const char* v = getenv(name); return v && *v && *v != '0'; }
-inline bool env_not_off(const char* name) { const char* v = getenv(name); return !(v && *v == '0'); }
-inline uint64_t env_uint(const char* name, uint64_t dflt, int base) {
-  const char* v = getenv(name);
-  return v && *v ? strtoull(v, nullptr, base) : dflt;
 }
 
 }  // namespace tg

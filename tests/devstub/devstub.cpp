@@ -15,9 +15,19 @@
 // host memory, copies and memsets are performed, kernels do nothing: the audit
 // is about which device each call reaches, not about results.
 //
+//
+// Launch trace (tests/test_batch_plan_trace.py): between devstub_trace_begin and
+// devstub_trace_take every launcher, allocation call, async memset / copy and
+// stream synchronize appends one line, its name and arguments.  Pointers are
+// written as null, a<k>+<byte offset> (the k-th distinct allocation in order of
+// first appearance in this trace) or ext (memory the stub did not allocate);
+// streams as s<k> the same way, so a trace depends on neither addresses nor on
+// what ran before it.  Off by default.
+//
 // Test-only; never shipped or loaded by the product.
 #include <hip/hip_runtime_api.h>
 
+#include <atomic>
 #include <cstdarg>
 #include <cstdio>
 #include <cstdlib>
@@ -63,6 +73,40 @@ std::map<const void*, int> g_events;        // event -> device
 std::vector<std::string> g_violations;
 uint64_t g_checked = 0;                     // stream-ordered calls checked
 uint64_t g_pinned_cross = 0;                // pinned memory of one device used by another's work
+
+// the opt-in trace (all under g_mu): devstub_trace_begin turns it on for the
+// calling thread, or for every thread (the EVP queue launches on its dispatcher)
+thread_local bool t_trace = false;
+std::atomic<bool> g_trace_all{false};
+std::string g_trace;
+std::map<uintptr_t, int> g_trace_allocs;    // allocation base -> k of a<k>
+std::map<const void*, int> g_trace_streams; // stream -> k of s<k>
+bool tracing() { return t_trace || g_trace_all.load(std::memory_order_relaxed); }
+
+std::string fmt(const char* f, ...) {
+  char buf[256];
+  va_list ap;
+  va_start(ap, f);
+  vsnprintf(buf, sizeof buf, f, ap);
+  va_end(ap);
+  return buf;
+}
+// a pointer as the trace writes it
+std::string tptr(const void* p) {
+  if (!p) return "null";
+  const uintptr_t a = (uintptr_t)p;
+  auto it = g_allocs.upper_bound(a);
+  if (it == g_allocs.begin()) return "ext";
+  --it;
+  if (a >= it->first + (it->second.size ? it->second.size : 1)) return "ext";
+  const int k = g_trace_allocs.emplace(it->first, (int)g_trace_allocs.size()).first->second;
+  return fmt("a%d+%llu", k, (unsigned long long)(a - it->first));
+}
+std::string tstream(hipStream_t s) {
+  if (!s) return "null";
+  return fmt("s%d", g_trace_streams.emplace(s, (int)g_trace_streams.size()).first->second);
+}
+void trace_line(const std::string& l) { g_trace += l + "\n"; }
 
 void violation(const char* fmt, ...) {
   char buf[512];
@@ -118,6 +162,7 @@ void* alloc(size_t n, bool pinned) {
   if (p) {
     memset(p, 0, n ? n : 1);
     g_allocs[(uintptr_t)p] = Alloc{n, t_dev, pinned};
+    g_trace_allocs.erase((uintptr_t)p);  // an address used again is a new allocation
   }
   return p;
 }
@@ -181,6 +226,7 @@ hipError_t hipMalloc(void** p, size_t n) {
   rt_enter("hipMalloc");
   std::lock_guard<std::mutex> lk(g_mu);
   *p = alloc(n, false);
+  if (tracing()) trace_line(fmt("hipMalloc bytes=%zu -> ", n) + tptr(*p));
   return *p ? hipSuccess : hipErrorOutOfMemory;
 }
 hipError_t hipMallocAsync(void** p, size_t n, hipStream_t s) {
@@ -188,17 +234,20 @@ hipError_t hipMallocAsync(void** p, size_t n, hipStream_t s) {
   std::lock_guard<std::mutex> lk(g_mu);
   stream_dev("hipMallocAsync", s);
   *p = alloc(n, false);
+  if (tracing()) trace_line(fmt("hipMallocAsync bytes=%zu s=", n) + tstream(s) + " -> " + tptr(*p));
   return *p ? hipSuccess : hipErrorOutOfMemory;
 }
 hipError_t hipFree(void* p) {
   rt_enter("hipFree");
   std::lock_guard<std::mutex> lk(g_mu);
+  if (tracing()) trace_line("hipFree " + tptr(p));
   return release(p, false, "hipFree");
 }
 hipError_t hipFreeAsync(void* p, hipStream_t s) {
   rt_enter("hipFreeAsync");
   std::lock_guard<std::mutex> lk(g_mu);
   stream_dev("hipFreeAsync", s);
+  if (tracing()) trace_line("hipFreeAsync " + tptr(p) + " s=" + tstream(s));
   return release(p, false, "hipFreeAsync");
 }
 hipError_t hipHostMalloc(void** p, size_t n, unsigned int) {
@@ -234,8 +283,14 @@ hipError_t hipStreamDestroy(hipStream_t s) {
   delete reinterpret_cast<char*>(s);
   return hipSuccess;
 }
-hipError_t hipStreamSynchronize(hipStream_t) {
-  rt_enter("hipStreamSynchronize"); return hipSuccess; }
+hipError_t hipStreamSynchronize(hipStream_t s) {
+  rt_enter("hipStreamSynchronize");
+  if (tracing()) {
+    std::lock_guard<std::mutex> lk(g_mu);
+    trace_line("hipStreamSynchronize s=" + tstream(s));
+  }
+  return hipSuccess;
+}
 hipError_t hipStreamWaitEvent(hipStream_t s, hipEvent_t e, unsigned int) {
   rt_enter("hipStreamWaitEvent");
   std::lock_guard<std::mutex> lk(g_mu);
@@ -285,13 +340,16 @@ hipError_t hipMemcpy(void* d, const void* s, size_t n, hipMemcpyKind) {
   if (n) memmove(d, s, n);
   return hipSuccess;
 }
-hipError_t hipMemcpyAsync(void* d, const void* s, size_t n, hipMemcpyKind, hipStream_t st) {
+hipError_t hipMemcpyAsync(void* d, const void* s, size_t n, hipMemcpyKind kind, hipStream_t st) {
   rt_enter("hipMemcpyAsync");
   {
     std::lock_guard<std::mutex> lk(g_mu);
     const int dev = stream_dev("hipMemcpyAsync", st);
     mem_on("hipMemcpyAsync", "dst", d, dev);
     mem_on("hipMemcpyAsync", "src", s, dev);
+    if (tracing())
+      trace_line("hipMemcpyAsync dst=" + tptr(d) + " src=" + tptr(s) +
+                 fmt(" bytes=%zu kind=%d s=", n, (int)kind) + tstream(st));
   }
   if (n) memmove(d, s, n);
   return hipSuccess;
@@ -310,6 +368,8 @@ hipError_t hipMemsetAsync(void* p, int v, size_t n, hipStream_t s) {
   {
     std::lock_guard<std::mutex> lk(g_mu);
     mem_on("hipMemsetAsync", "dst", p, stream_dev("hipMemsetAsync", s));
+    if (tracing())
+      trace_line("hipMemsetAsync dst=" + tptr(p) + fmt(" value=%d bytes=%zu s=", v, n) + tstream(s));
   }
   if (n) memset(p, v, n);
   return hipSuccess;
@@ -319,6 +379,8 @@ hipError_t hipMemsetD32Async(hipDeviceptr_t p, int v, size_t n, hipStream_t s) {
   {
     std::lock_guard<std::mutex> lk(g_mu);
     mem_on("hipMemsetD32Async", "dst", p, stream_dev("hipMemsetD32Async", s));
+    if (tracing())
+      trace_line("hipMemsetD32Async dst=" + tptr(p) + fmt(" value=%d count=%zu s=", v, n) + tstream(s));
   }
   for (size_t i = 0; i < n; i++) reinterpret_cast<int32_t*>(p)[i] = v;
   return hipSuccess;
@@ -353,75 +415,125 @@ int devstub_report(char* buf, size_t n, uint64_t* checked, uint64_t* pinned_cros
   return (int)g_violations.size();
 }
 
+// The launch trace.  begin: start an empty trace of the calling thread's stub
+// calls (all_threads != 0: of every thread's).  take: stop, copy the trace
+// (NUL-terminated, cut to n) into buf and return its full length.
+void devstub_trace_begin(int all_threads) {
+  std::lock_guard<std::mutex> lk(g_mu);
+  g_trace.clear();
+  g_trace_allocs.clear();
+  g_trace_streams.clear();
+  t_trace = true;
+  g_trace_all.store(all_threads != 0);
+}
+size_t devstub_trace_take(char* buf, size_t n) {
+  std::lock_guard<std::mutex> lk(g_mu);
+  t_trace = false;
+  g_trace_all.store(false);
+  if (buf && n) snprintf(buf, n, "%s", g_trace.c_str());
+  return g_trace.size();
+}
+
 }  // extern "C"
 
 // ---------------------------------------------------------------------------
 // kernel launchers: check the stream and the device memory each kernel reads
-// or writes; run nothing
+// or writes, trace the arguments; run nothing
 namespace tg {
 namespace {
-int launch(const char* what, hipStream_t s, std::initializer_list<std::pair<const char*, const void*>> mem) {
+using Mem = std::initializer_list<std::pair<const char*, const void*>>;
+// `scalars`: the launcher's own scalar arguments, for the trace
+int launch(const char* what, hipStream_t s, Mem mem, const std::string& scalars = "") {
   std::lock_guard<std::mutex> lk(g_mu);
   const int d = stream_dev(what, s);
   for (const auto& m : mem) mem_on(what, m.first, m.second, d);
+  if (tracing()) {
+    std::string l = std::string(what) + " s=" + tstream(s) + scalars;
+    for (const auto& m : mem) l += std::string(" ") + m.first + "=" + tptr(m.second);
+    trace_line(l);
+  }
   return 0;
 }
-int launch_batch(const char* what, const BatchArgs& a, hipStream_t s,
-                 std::initializer_list<std::pair<const char*, const void*>> more = {}) {
+int launch_batch(const char* what, const BatchArgs& a, hipStream_t s, const std::string& scalars,
+                 Mem more = {}) {
   std::lock_guard<std::mutex> lk(g_mu);
   const int d = stream_dev(what, s);
   const std::pair<const char*, const void*> mem[] = {
       {"sessions", a.sessions}, {"gcm_tables", a.gcm_tables}, {"descs", a.descs}, {"in", a.in},
       {"out", a.out}, {"status", a.status}, {"sel", a.sel}, {"wg_next", a.wg_next}, {"dbg", a.dbg},
-      {"cut_work", a.cut_work}, {"pieces", a.pieces}};
+      {"cut_work", a.cut_work}, {"pieces", a.pieces}, {"n_pieces", a.n_pieces},
+      {"wg_times", a.wg_times}, {"type_out", a.type_out}};
   for (const auto& m : mem) mem_on(what, m.first, m.second, d);
   for (const auto& m : more) mem_on(what, m.first, m.second, d);
+  if (tracing()) {
+    std::string l = std::string(what) + " s=" + tstream(s) + scalars;
+    for (const auto& m : more) l += std::string(" ") + m.first + "=" + tptr(m.second);
+    l += " |";  // every field of BatchArgs
+    for (const auto& m : mem) l += std::string(" ") + m.first + "=" + tptr(m.second);
+    l += fmt(" n=%u records_per_group=%u n_sessions=%u bs_reserve=%u hy_flags=%u bs16_min=%u",
+             a.n, a.records_per_group, a.n_sessions, a.bs_reserve, a.hy_flags, a.bs16_min);
+    l += fmt(" pack=%u pws=%u fused=%u in_bytes=%llu out_bytes=%llu cut_snap=%u tls13=%u", a.pack,
+             a.pws, a.fused, (unsigned long long)a.in_bytes, (unsigned long long)a.out_bytes,
+             a.cut_snap, a.tls13);
+    trace_line(l);
+  }
   return 0;
 }
 }  // namespace
 
-int launch_gcm(const BatchArgs& a, bool, bool, int, int, hipStream_t s) {
-  return launch_batch("launch_gcm", a, s);
+int launch_gcm(const BatchArgs& a, bool seal, bool raw, int rounds, int groups, hipStream_t s) {
+  return launch_batch("launch_gcm", a, s,
+                      fmt(" seal=%d raw=%d rounds=%d groups=%d", seal, raw, rounds, groups));
 }
-int launch_gcm_split(const BatchArgs& a, bool, int, hipStream_t s) {
-  return launch_batch("launch_gcm_split", a, s);
+int launch_gcm_split(const BatchArgs& a, bool seal, int rounds, hipStream_t s) {
+  return launch_batch("launch_gcm_split", a, s, fmt(" seal=%d rounds=%d", seal, rounds));
 }
-int launch_gcm_prep(const BatchArgs& a, RecPre* pre, bool, int, hipStream_t s) {
-  return launch_batch("launch_gcm_prep", a, s, {{"pre", pre}});
+int launch_gcm_prep(const BatchArgs& a, RecPre* pre, bool seal, int rounds, hipStream_t s) {
+  return launch_batch("launch_gcm_prep", a, s, fmt(" seal=%d rounds=%d", seal, rounds),
+                      {{"pre", pre}});
 }
-int launch_piece_plan(const BatchArgs& a, int, uint8_t* scratch, const uint2** pieces,
+int launch_piece_plan(const BatchArgs& a, int groups, uint8_t* scratch, const uint2** pieces,
                       const uint32_t** n_pieces, hipStream_t s) {
   *pieces = reinterpret_cast<const uint2*>(scratch);
   *n_pieces = reinterpret_cast<const uint32_t*>(scratch);
-  return launch_batch("launch_piece_plan", a, s, {{"scratch", scratch}});
+  return launch_batch("launch_piece_plan", a, s, fmt(" groups=%d", groups), {{"scratch", scratch}});
 }
-int launch_range_work(const BatchArgs& a, int, unsigned long long* out, hipStream_t s) {
-  return launch_batch("launch_range_work", a, s, {{"out", out}});
+int launch_range_work(const BatchArgs& a, int groups, unsigned long long* out, hipStream_t s) {
+  return launch_batch("launch_range_work", a, s, fmt(" groups=%d", groups), {{"out", out}});
 }
-int launch_gcm_queue(const BatchArgs& a, const RecPre* pre, bool, int, int, hipStream_t s) {
-  return launch_batch("launch_gcm_queue", a, s, {{"pre", pre}});
+int launch_gcm_queue(const BatchArgs& a, const RecPre* pre, bool seal, int rounds, int groups,
+                     hipStream_t s) {
+  return launch_batch("launch_gcm_queue", a, s,
+                      fmt(" seal=%d rounds=%d groups=%d", seal, rounds, groups), {{"pre", pre}});
 }
-int launch_gcm_stream(const DevSession* sessions, const DevGcmTables* tables, uint32_t, GcmStream* st,
-                      const GcmStreamOp* ops, uint32_t, hipStream_t s) {
-  return launch("launch_gcm_stream", s, {{"sessions", sessions}, {"tables", tables}, {"state", st}, {"ops", ops}});
+int launch_gcm_stream(const DevSession* sessions, const DevGcmTables* tables, uint32_t session,
+                      GcmStream* st, const GcmStreamOp* ops, uint32_t nops, hipStream_t s) {
+  return launch("launch_gcm_stream", s,
+                {{"sessions", sessions}, {"tables", tables}, {"state", st}, {"ops", ops}},
+                fmt(" session=%u nops=%u", session, nops));
 }
-int launch_chacha(const BatchArgs& a, bool, bool, bool, bool, hipStream_t s) {
-  return launch_batch("launch_chacha", a, s);
+int launch_chacha(const BatchArgs& a, bool seal, bool raw, bool rfc, bool old, hipStream_t s) {
+  return launch_batch("launch_chacha", a, s,
+                      fmt(" seal=%d raw=%d rfc=%d old=%d", seal, raw, rfc, old));
 }
-int launch_evp_server(const ServerArgs& a, int, hipStream_t s) {
-  return launch("launch_evp_server", s, {{"slots", a.slots}, {"stop", a.stop}, {"exited", a.exited}});
+int launch_evp_server(const ServerArgs& a, int groups, hipStream_t s) {
+  return launch("launch_evp_server", s, {{"slots", a.slots}, {"stop", a.stop}, {"exited", a.exited}},
+                fmt(" groups=%d nslots=%u seq=%u", groups, a.nslots, a.seq));
 }
 int launch_session_install_arg(DevSession* sessions, DevGcmTables* tables, const tlsgpu_session_params&,
-                               uint32_t, hipStream_t s) {
-  return launch("launch_session_install_arg", s, {{"sessions", sessions}, {"tables", tables}});
+                               uint32_t id, hipStream_t s) {
+  return launch("launch_session_install_arg", s, {{"sessions", sessions}, {"tables", tables}},
+                fmt(" id=%u", id));
 }
 int launch_session_install(DevSession* sessions, DevGcmTables* tables, const tlsgpu_session_params* p,
-                           uint32_t, uint32_t, hipStream_t s) {
-  return launch("launch_session_install", s, {{"sessions", sessions}, {"tables", tables}, {"params", p}});
+                           uint32_t first, uint32_t n, hipStream_t s) {
+  return launch("launch_session_install", s, {{"sessions", sessions}, {"tables", tables}, {"params", p}},
+                fmt(" first=%u n=%u", first, n));
 }
 int launch_upload_session(const void* img, DevSession* sess, DevGcmTables* tab, uint32_t table_bytes,
                           hipStream_t s) {
-  launch("launch_upload_session", s, {{"img", img}, {"sessions", sess}, {"tables", tab}});
+  launch("launch_upload_session", s, {{"img", img}, {"sessions", sess}, {"tables", tab}},
+         fmt(" table_bytes=%u", table_bytes));
   memcpy(sess, img, sizeof(DevSession));
   if (table_bytes) memcpy(tab, reinterpret_cast<const uint8_t*>(img) + sizeof(DevSession), table_bytes);
   return 0;
@@ -429,33 +541,47 @@ int launch_upload_session(const void* img, DevSession* sess, DevGcmTables* tab, 
 int launch_scrub_session(DevSession* sess, DevGcmTables* tab, hipStream_t s) {
   return launch("launch_scrub_session", s, {{"sessions", sess}, {"tables", tab}});
 }
-int launch_wire_frame(const tlsgpu_wire_stream* streams, uint32_t, const uint8_t* wire,
-                      const DevSession* sessions, uint32_t, uint32_t, tlsgpu_record* recs,
-                      tlsgpu_wire_result* results, uint32_t* total, hipStream_t s) {
-  return launch("launch_wire_frame", s, {{"streams", streams}, {"wire", wire}, {"sessions", sessions},
-                                         {"recs", recs}, {"results", results}, {"total", total}});
+int launch_wire_frame(const tlsgpu_wire_stream* streams, uint32_t n_streams, const uint8_t* wire,
+                      const DevSession* sessions, uint32_t n_sessions, uint32_t max_records,
+                      tlsgpu_record* recs, tlsgpu_wire_result* results, uint32_t* total, hipStream_t s) {
+  return launch("launch_wire_frame", s,
+                {{"streams", streams}, {"wire", wire}, {"sessions", sessions}, {"recs", recs},
+                 {"results", results}, {"total", total}},
+                fmt(" n_streams=%u n_sessions=%u max_records=%u", n_streams, n_sessions, max_records));
 }
-int launch_wire_seal_frame(const tlsgpu_write_stream* streams, uint32_t, const DevSession* sessions,
-                           uint32_t, uint8_t* wire, uint64_t, uint32_t, tlsgpu_record* recs,
+int launch_wire_seal_frame(const tlsgpu_write_stream* streams, uint32_t n_streams,
+                           const DevSession* sessions, uint32_t n_sessions, uint8_t* wire,
+                           uint64_t wire_bytes, uint32_t max_records, tlsgpu_record* recs,
                            tlsgpu_write_result* results, uint32_t* total, hipStream_t s) {
-  return launch("launch_wire_seal_frame", s, {{"streams", streams}, {"sessions", sessions}, {"wire", wire},
-                                              {"recs", recs}, {"results", results}, {"total", total}});
+  return launch("launch_wire_seal_frame", s,
+                {{"streams", streams}, {"sessions", sessions}, {"wire", wire}, {"recs", recs},
+                 {"results", results}, {"total", total}},
+                fmt(" n_streams=%u n_sessions=%u wire_bytes=%llu max_records=%u", n_streams,
+                    n_sessions, (unsigned long long)wire_bytes, max_records));
 }
-int launch_wire_finish(uint32_t, tlsgpu_wire_result* results, int32_t* status, hipStream_t s) {
-  return launch("launch_wire_finish", s, {{"results", results}, {"status", status}});
+int launch_wire_finish(uint32_t n_streams, tlsgpu_wire_result* results, int32_t* status, hipStream_t s) {
+  return launch("launch_wire_finish", s, {{"results", results}, {"status", status}},
+                fmt(" n_streams=%u", n_streams));
 }
-int launch_fill_synthetic(uint8_t* d_out, uint64_t, uint32_t, uint32_t, uint64_t, uint64_t, hipStream_t s) {
-  return launch("launch_fill_synthetic", s, {{"out", d_out}});
+int launch_fill_synthetic(uint8_t* d_out, uint64_t stride, uint32_t span_len, uint32_t n, uint64_t seed,
+                          uint64_t index0, hipStream_t s) {
+  return launch("launch_fill_synthetic", s, {{"out", d_out}},
+                fmt(" stride=%llu span_len=%u n=%u seed=%llu index0=%llu", (unsigned long long)stride,
+                    span_len, n, (unsigned long long)seed, (unsigned long long)index0));
 }
-int launch_fill_synthetic_spans(uint8_t* d_out, const uint64_t* offs, const uint32_t* lens, uint32_t,
-                                uint64_t, uint64_t, hipStream_t s) {
-  return launch("launch_fill_synthetic_spans", s, {{"out", d_out}, {"offs", offs}, {"lens", lens}});
+int launch_fill_synthetic_spans(uint8_t* d_out, const uint64_t* offs, const uint32_t* lens, uint32_t n,
+                                uint64_t seed, uint64_t index0, hipStream_t s) {
+  return launch("launch_fill_synthetic_spans", s, {{"out", d_out}, {"offs", offs}, {"lens", lens}},
+                fmt(" n=%u seed=%llu index0=%llu", n, (unsigned long long)seed,
+                    (unsigned long long)index0));
 }
 int launch_check_bounds(const tlsgpu_record* recs, tlsgpu_record* safe, uint32_t n, const DevSession* sessions,
-                        uint32_t, uint64_t, uint64_t, bool, int32_t* status, uint32_t* ctl, uint32_t,
-                        hipStream_t s) {
-  launch("launch_check_bounds", s, {{"recs", recs}, {"safe", safe}, {"sessions", sessions},
-                                    {"status", status}, {"ctl", ctl}});
+                        uint32_t n_sessions, uint64_t in_bytes, uint64_t out_bytes, bool seal,
+                        int32_t* status, uint32_t* ctl, uint32_t ctl_words, hipStream_t s) {
+  launch("launch_check_bounds", s,
+         {{"recs", recs}, {"safe", safe}, {"sessions", sessions}, {"status", status}, {"ctl", ctl}},
+         fmt(" n=%u n_sessions=%u in_bytes=%llu out_bytes=%llu seal=%d ctl_words=%u", n, n_sessions,
+             (unsigned long long)in_bytes, (unsigned long long)out_bytes, seal, ctl_words));
   // the engine's later kernels read the sanitized copy: give them the input's
   if (n && safe && recs) memmove(safe, recs, sizeof(tlsgpu_record) * (size_t)n);
   return 0;

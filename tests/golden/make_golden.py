@@ -25,8 +25,15 @@ Inputs (read-only, never copied as source):
     record state it used (SSL_AEAD_CTX fields, ssl_locl.h:527-543; the key
     handed to EVP_AEAD_CTX_init; s3->write_sequence), for the four AEAD suites.
 
+  * --batch-plan: no reference input.  The engine's host objects as they are
+    in the tree, linked with the recording HIP stub (tests/devstub), run every
+    case of tests/test_batch_plan_trace.py; the digest of each case's launch
+    trace goes to batch_plan_trace.json.  Record it from the sources whose
+    launches are to be kept (before a change to run_batch), never after.
+
 Outputs: aeadtests.txt, gcm128_vectors.json, chacha_vectors.json,
-poly1305_vectors.json, records.json, batch_digests.json, wire_ref.json.
+poly1305_vectors.json, records.json, batch_digests.json, wire_ref.json,
+batch_plan_trace.json (--batch-plan only).
 """
 from __future__ import annotations
 
@@ -40,7 +47,8 @@ import sys
 HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(os.path.dirname(HERE))
 sys.path.insert(0, os.path.join(ROOT, "oracle"))
-import pyoracle as po  # noqa: E402
+if "--batch-plan" not in sys.argv:  # that recorder needs no reference build
+    import pyoracle as po  # noqa: E402
 
 REFT = "/root/reference/src/libressl-2.4.1/tests"
 
@@ -237,7 +245,23 @@ def make_wire_ref():
             "suites": suites}
 
 
+def make_batch_plan_trace():
+    """{child: {case id: digest}} of tests/test_batch_plan_trace.py, one child per line."""
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import test_batch_plan_trace as bpt
+    bpt.build_stub()
+    got = bpt.run_children()
+    body = ",\n".join(json.dumps(c) + ":" + json.dumps(got[c], separators=(",", ":"))
+                      for c in got)
+    with open(os.path.join(HERE, "batch_plan_trace.json"), "w") as f:
+        f.write("{\n" + body + "\n}\n")
+    print({c: len(v) for c, v in got.items()})
+
+
 def main():
+    if len(sys.argv) > 1 and sys.argv[1] == "--batch-plan":
+        make_batch_plan_trace()
+        return
     if len(sys.argv) > 1 and sys.argv[1] == "--wire":
         json.dump(make_wire_ref(), open(os.path.join(HERE, "wire_ref.json"), "w"))
         return

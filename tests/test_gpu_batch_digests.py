@@ -52,7 +52,7 @@ def test_batch_digest_matches_reference(ta, engine, name):
     digest of that slice of the batch."""
     from talos_amd.workload import Workload, zipf_lengths
     # ":hinted": the batch-shape hints bench.py states (talos_amd.batch_hints),
-    # so B and D run the fused queue kernel (engine.cpp run_batch `fused`)
+    # so B and D run the fused queue kernel (batch.cpp run_batch `fused`)
     name, _, hinted = name.partition(":")
     d = _batches()[name]
     kind = ta.AEAD_NAMES[d["aead"]]

@@ -584,7 +584,7 @@ def test_batch_fused_prologue(ta, engine, oracle, gcm_impl, mode, hints, name):
 
 @pytest.mark.parametrize("mode", ["open", "seal"])
 def test_batch_fused_chacha(ta, engine, oracle, mode):
-    """The fused ChaCha batch (round 5, engine.cpp run_batch `fused_cc`): a
+    """The fused ChaCha batch (round 5, batch.cpp run_batch `fused_cc`): a
     table of RFC 7539 ChaCha20-Poly1305 sessions only, so the staged ChaCha
     kernel is the batch's only launch and checks bounds and writes the statuses
     of the records it does not run itself (no check_record_bounds, no
@@ -593,7 +593,7 @@ def test_batch_fused_chacha(ta, engine, oracle, mode):
 
 
 def _fused_case(ta, engine, oracle, mode, hints, name, lengths=None):
-    """The fused queue kernel (round 5, engine.cpp run_batch `fused`): one AES
+    """The fused queue kernel (round 5, batch.cpp run_batch `fused`): one AES
     key size installed and SESSION_RUNS stated, so the queue kernel is the
     batch's only launch and checks bounds, writes the initial statuses and
     derives each record's constants in its own prologue (no
@@ -665,7 +665,7 @@ SKEWED_LENGTHS = [16384] + [17, 16, 15, 12, 9] * 7 + [3, 5, 1, 0]
 @pytest.mark.parametrize("balance,snap,pieces", [("1", "0", "0"), ("2", "0", "0"), ("2", "300", "0"),
                                                  ("0", "0", "2")])
 def test_batch_fused_balanced_ranges(ta, balance, snap, pieces):
-    """Work-balanced ranges (round 5, engine.cpp run_batch `balance`,
+    """Work-balanced ranges (round 5, batch.cpp run_batch `balance`,
     gcm_hybrid.h work_cut): the fused kernel's workgroups take the records
     between cuts at equal work (payload bytes + 256 per record) instead of
     equal counts (opt-in, measured no faster on config D).  TLSGPU_BALANCE=1

@@ -42,7 +42,7 @@ def main():
                   tamper_every=1024)
     desc_len = wl.lengths + ta.EXPLICIT_NONCE_LEN[kind] + ta.TAG_LEN
     wl.table.hint(ta.batch_hints(desc_len, wl.session, seal=False))
-    groups = eng.num_cus                  # engine.cpp groups_for
+    groups = eng.num_cus                  # batch.cpp groups_for
     if groups * 16 > per_gpu:
         groups = (per_gpu + 15) // 16
     rpg = (per_gpu + groups - 1) // groups
