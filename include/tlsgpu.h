@@ -102,10 +102,14 @@ enum tlsgpu_aead {
  * and the AAD is the record header 0x17 0x03 0x03 BE16(ciphertext length with
  * the tag); the descriptor's type bits do not enter it.
  * seal: in_off / length are the content and the type bits the INNER content
- *       type.  The engine encrypts content || type (no padding: a padding policy
- *       is out of scope, as with LibreSSL's and OpenSSL's defaults) and writes
- *       ciphertext || tag(16) at out_off; status = length + 1 + 16.  The type
- *       byte is synthesized: d_in is never read past in_off + length.
+ *       type.  The engine encrypts content || type || zeros, padded to the
+ *       session's pad_block (RFC 8446 5.4; OpenSSL's block padding rule):
+ *         inner = length + 1                     pad_block <= 1 or length >= 16384
+ *         inner = roundup(length + 1, pad_block) otherwise
+ *       and writes ciphertext || tag(16), inner + 16 bytes, at out_off; status
+ *       = inner + 16 and the AAD's length field is inner + 16.  Without a
+ *       padding block that is length + 1 + 16.  The type byte and the zeros
+ *       are synthesized: d_in is never read past in_off + length.
  * open: length is the fragment, ciphertext || tag.  The decrypted
  *       TLSInnerPlaintext (length - 16 bytes, its zero padding included) is
  *       written at out_off (in place: out_off = in_off).  status = the CONTENT
@@ -117,8 +121,8 @@ enum tlsgpu_aead {
  * TLSGPU_MAX_RECORD bounds the inner plaintext, and the bounds rule of
  * TLSGPU_REC_OUT_OF_BOUNDS uses these spans.  All of this holds for the three
  * TLS 1.3 kinds alike (ChaCha20-Poly1305: RFC 7905's nonce is RFC 8446's).
- * Limits: no padding on seal, post-handshake records only (the compatibility
- * ChangeCipherSpec of a handshake is the caller's to skip). */
+ * Limits: post-handshake records only (the compatibility ChangeCipherSpec of a
+ * handshake is the caller's to skip). */
 typedef struct tlsgpu_record {
 	uint64_t in_off;
 	uint64_t out_off;
@@ -139,7 +143,9 @@ typedef struct tlsgpu_session_params {
 	uint8_t fixed_iv[12];
 	uint32_t tag_len;		/* 0 = default 16 (EVP_AEAD_DEFAULT_TAG_LENGTH) */
 	uint16_t version;		/* s->version, e.g. 0x0303; 0x0304: a TLS 1.3 session */
-	uint16_t reserved;
+	uint16_t pad_block;		/* version 0x0304 only (ignored otherwise): seal pads
+					 * the inner plaintext to a multiple of this; 0, 1 =
+					 * no padding, else a power of two, 2..16384 */
 } tlsgpu_session_params;
 /* A TLS 1.3 session is aead = TLSGPU_AES_128_GCM / _256_GCM /
  * TLSGPU_CHACHA20_POLY1305_TLS13, version = 0x0304, fixed_iv_len = 12 (the
@@ -149,6 +155,11 @@ typedef struct tlsgpu_session_params {
  * so is TLSGPU_CHACHA20_POLY1305_TLS13 with any other version, a key_len other
  * than 32, another fixed_iv_len or tag_len.  Every other version behaves as
  * before.  The three TLS 1.3 kinds share tables and batches.
+ * pad_block is the session's record padding policy (the rule under "TLS 1.3
+ * sessions" above; what OpenSSL's SSL_CTX_set_block_padding / RecordPadding
+ * do).  It is read for version 0x0304 only.  Powers of two only, and anything
+ * else is TLSGPU_EINVAL at install, is a deliberate limit: the padded length is
+ * derived per record in several kernels, and a mask keeps a division out of them.
  * One session table holds one generation: the GCM kernels are compiled once
  * per record layout (carrying the layout as per-session data cost the TLS 1.2
  * queue kernel's pack variants spilled registers), so the
@@ -201,8 +212,11 @@ int tlsgpu_seal_batch(tlsgpu_sessions *t, const tlsgpu_record *d_recs, uint32_t 
  *   TLSGPU_HINT_NO_SHORT_RECORDS  no GCM record of <= 62 blocks (open: length
  *                                 <= 1,016 B with the 8-B explicit nonce and a
  *                                 16-B tag; TLS 1.3: 62 blocks of inner
- *                                 plaintext, seal length <= 991 B, open length
- *                                 <= 1,008 B): the pack variant is not launched;
+ *                                 plaintext, open length <= 1,008 B, seal: the
+ *                                 PADDED inner plaintext <= 992 B, i.e. length
+ *                                 <= 991 B without a padding block and never
+ *                                 with pad_block >= 1024): the pack variant is
+ *                                 not launched;
  *   TLSGPU_HINT_SESSION_RUNS      records come in session runs of >= 12
  *                                 records on average: the per-wave-session
  *                                 kernel is not launched.
@@ -423,9 +437,10 @@ int tlsgpu_open_wire(tlsgpu_sessions *t, const tlsgpu_wire_stream *d_streams,
  * (TLSGPU_REC_OUT_OF_BOUNDS).  tlsgpu_seal_wire_size gives a stream's wire
  * bytes.  Asynchronous.
  * A TLS 1.3 session of any kind: each fragment (<= max_fragment <= 16384) goes out as the
- * header 17 03 03 BE16(len + 17) and ciphertext(content || type) || tag, with
- * stream.type as the inner type; next_seq and wire_len follow that framing
- * (tlsgpu_seal_wire_size_v). */
+ * header 17 03 03 BE16(inner + 16) and ciphertext(content || type || zeros) ||
+ * tag, inner = the fragment's padded inner plaintext under the session's
+ * pad_block (len + 1 without one), with stream.type as the inner type;
+ * next_seq and wire_len follow that framing (tlsgpu_seal_wire_size_p). */
 typedef struct tlsgpu_write_stream {
 	uint64_t data_off;	/* application data at d_data + data_off */
 	uint64_t wire_off;	/* the stream's records go to d_wire + wire_off */
@@ -463,6 +478,12 @@ uint64_t tlsgpu_seal_wire_size(int aead, uint32_t data_len, uint32_t max_fragmen
  * no install accepts, keeps the TLS 1.2 arithmetic). */
 uint64_t tlsgpu_seal_wire_size_v(int aead, uint16_t version, uint32_t data_len,
     uint32_t max_fragment, uint32_t tag_len);
+/* The same for a session installed with `pad_block`: under TLS 1.3 framing each
+ * record is 5 + inner + 16 with the fragment's padded inner plaintext length.
+ * Equal to tlsgpu_seal_wire_size_v for pad_block <= 1 and for any session that
+ * is not TLS 1.3 (pad_block is ignored there, as at install). */
+uint64_t tlsgpu_seal_wire_size_p(int aead, uint16_t version, uint32_t data_len,
+    uint32_t max_fragment, uint32_t tag_len, uint32_t pad_block);
 
 /* GCM TLS batch kernel selection (process-wide; results are identical).
  * TLSGPU_GCM_AUTO (default): TLSGPU_GCM_SPLIT for batches of at most two

@@ -11,6 +11,12 @@ events); prints one JSON line per (shape, generation, op) and the ratios.
 
     python scripts/tls13_cost.py [--shape B|C|D|BD|...] [--gen 12|13|both] [--steps K] [--warmup W]
 
+--pad B (TLS 1.3 seals only): what record padding costs.  Each shape is sealed
+twice in the same process: by sessions with pad_block = B, and by sessions
+without padding whose records have the content length of the padded ones
+(inner - 1), so both write the same number of bytes; the difference is the
+price of the padding blocks taking the kernels' tail paths.
+
 Under `rocprofv3 --kernel-trace --stats -- python scripts/tls13_cost.py --gen 13
 --steps 3` the stats list tg::tls13_unpad_kernel, the unpad pass's own time
 (--shape C: the ChaCha sessions' pass).
@@ -33,18 +39,26 @@ SHAPES = {"B": (ta.AES_128_GCM, 65536, 1024, None, 0x5EED0001),
 GIB = float(1 << 30)
 
 
-def run(engine, shape, gen, steps, warmup):
+def run(engine, shape, gen, steps, warmup, pad=0, as_padded=0):
+    """pad: the sessions' pad_block; as_padded: no padding, but every record as
+    long as pad_block = as_padded would make it (both: TLS 1.3, seal only)."""
     kind, n, nsess, dist, seed = SHAPES[shape]
     t13 = gen == 13
     lens = (np.full(n, 16384, dtype=np.int64) if dist is None
             else zipf_lengths(n, seed) if dist == "zipf" else np.full(n, dist, dtype=np.int64))
+    inner_of = np.vectorize(ta.tls13_inner_len)
+    if as_padded:
+        lens = inner_of(lens, as_padded).astype(np.int64) - 1
     chacha = kind == ta.CHACHA20_POLY1305
     if chacha and t13:
         kind = ta.CHACHA20_POLY1305_TLS13     # the same cipher, key and 12-byte IV
     eiv, extra = (0, 1) if t13 else (0 if chacha else 8, 0)
+    if pad:
+        extra = inner_of(lens, pad).astype(np.int64) - lens      # type byte + padding, per record
     params = [ta.SessionParams(kind, fill_bytes(seed ^ KEY_TAG, s, ta.KEY_LEN[kind]),
                                fill_bytes(seed ^ IV_TAG, s, 12 if t13 or chacha else 4),
-                               version=0x0304 if t13 else 0x0303) for s in range(nsess)]
+                               version=0x0304 if t13 else 0x0303, pad_block=pad)
+              for s in range(nsess)]
     table = ta.SessionTable(engine, nsess)
     table.install(0, params)
     session = (np.arange(n) // (n // nsess)).astype(np.uint32)
@@ -79,7 +93,10 @@ def run(engine, shape, gen, steps, warmup):
     for op, descs, lengths, d_i, d_o, want in (
             ("seal", d_seal, lens, d_pt, d_body, frag.astype(np.int32)),
             ("open", d_open, frag, d_body, d_out, lens.astype(np.int32))):
-        table.hint(ta.batch_hints(lengths, session, op == "seal", tls13=t13))
+        if (pad or as_padded) and op == "open":
+            continue
+        table.hint(ta.batch_hints(lengths, session, op == "seal", tls13=t13,
+                                  pad_blocks={s: pad for s in range(nsess)} if pad else None))
         fn = ta.seal_batch if op == "seal" else ta.open_batch
 
         def launch():
@@ -100,10 +117,13 @@ def run(engine, shape, gen, steps, warmup):
         e1.close()
         results[op] = ms
         print(json.dumps({"shape": shape, "tls": "1.3" if t13 else "1.2", "op": op, "records": n,
+                          **({"pad_block": pad} if pad else {}),
+                          **({"lengths_as_padded_to": as_padded} if as_padded else {}),
+                          "wire_bytes": int(frag.astype(np.int64).sum()),
                           "payload_bytes": int(lens.sum()), "ms_per_launch": round(ms, 4),
                           "GiBps": round(float(lens.sum()) / (ms / 1e3) / GIB, 2),
                           "steps": steps, "warmup": warmup}), flush=True)
-    if t13:   # spot check: the opened content and inner type of a few records
+    if t13 and "open" in results:   # spot check: the opened content and inner type of a few records
         for i in (0, n // 2, n - 1):
             got = d_out.download(int(lens[i]) + 1, int(out_off[i]))
             ref = d_pt.download(int(lens[i]), int(pt_off[i]))
@@ -120,10 +140,18 @@ def main():
     ap.add_argument("--gen", default="both", choices=["12", "13", "both"])
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=10)
+    ap.add_argument("--pad", type=int, default=0, metavar="B",
+                    help="TLS 1.3 seals with pad_block = B against unpadded records of the padded lengths")
     a = ap.parse_args()
     ta.load_library()
     engine = ta.Engine(0)
-    for shape in a.shape:
+    for shape in a.shape if a.pad else "":
+        padded = run(engine, shape, 13, a.steps, a.warmup, pad=a.pad)["seal"]
+        plain = run(engine, shape, 13, a.steps, a.warmup, as_padded=a.pad)["seal"]
+        print(json.dumps({"shape": shape, "pad_block": a.pad,
+                          "padded_over_unpadded_same_lengths_time": round(padded / plain, 4)}),
+              flush=True)
+    for shape in "" if a.pad else a.shape:
         res = {g: run(engine, shape, g, a.steps, a.warmup)
                for g in ((12, 13) if a.gen == "both" else (int(a.gen),))}
         if len(res) == 2:

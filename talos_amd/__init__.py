@@ -83,7 +83,7 @@ class TlsGpuError(RuntimeError):
 class _SessionParams(C.Structure):
     _fields_ = [("aead", C.c_int32), ("key_len", C.c_uint32), ("key", C.c_uint8 * 32),
                 ("fixed_iv_len", C.c_uint32), ("fixed_iv", C.c_uint8 * 12),
-                ("tag_len", C.c_uint32), ("version", C.c_uint16), ("reserved", C.c_uint16)]
+                ("tag_len", C.c_uint32), ("version", C.c_uint16), ("pad_block", C.c_uint16)]
 
 
 @dataclass
@@ -93,6 +93,7 @@ class SessionParams:
     fixed_iv: bytes = b""
     tag_len: int = 0
     version: int = 0x0303
+    pad_block: int = 0  # TLS 1.3 (version 0x0304) seal padding block: 0 / 1 none, else 2^k <= 16384
 
     def to_c(self) -> _SessionParams:
         p = _SessionParams()
@@ -104,6 +105,7 @@ class SessionParams:
             C.memmove(p.fixed_iv, self.fixed_iv, len(self.fixed_iv))
         p.tag_len = self.tag_len
         p.version = self.version
+        p.pad_block = self.pad_block
         return p
 
 
@@ -152,6 +154,7 @@ def load_library(path: str = LIBPATH) -> C.CDLL:
                                    vp, vp]),
         "tlsgpu_seal_wire_size": (u64, [i32, u32, u32, u32]),
         "tlsgpu_seal_wire_size_v": (u64, [i32, C.c_uint16, u32, u32, u32]),
+        "tlsgpu_seal_wire_size_p": (u64, [i32, C.c_uint16, u32, u32, u32, u32]),
         "tlsgpu_host_pipeline": (i32, [vp, C.c_uint, C.c_size_t]),
         "tlsgpu_seal_host": (i32, [vp, vp, u32, vp, C.c_size_t, vp, C.c_size_t, vp]),
         "tlsgpu_sessions_set_owner": (i32, [vp, u32, u32, vp]),
@@ -406,18 +409,32 @@ class SessionTable:
 HINT_NO_SHORT_RECORDS, HINT_SESSION_RUNS = 1, 2
 
 
-def batch_hints(lengths, sessions, seal: bool, tls13: bool = False) -> int:
+def tls13_inner_len(length: int, pad_block: int = 0) -> int:
+    """Inner plaintext length of a TLS 1.3 seal of `length` content bytes under a
+    session's pad_block (tlsgpu.h: content + type, rounded up to the block;
+    content of 16384 bytes or more is never padded)."""
+    if pad_block <= 1 or length >= 16384:
+        return length + 1
+    return (length + pad_block) // pad_block * pad_block
+
+
+def batch_hints(lengths, sessions, seal: bool, tls13: bool = False, pad_blocks=None) -> int:
     """The hints a caller that built the batch can state (tlsgpu.h): no GCM
     record short enough for a pack, session runs of >= 12 records on average.
     `lengths` are the descriptors' length fields, as the engine's host_hints
     reads them: fragment lengths (explicit nonce + ciphertext + tag) for an
     open, plaintext lengths for a seal.  tls13: 62 blocks of inner plaintext
-    (content + type byte) without an explicit nonce."""
+    (content + type byte) without an explicit nonce.  pad_blocks (a TLS 1.3
+    seal): {session: pad_block} of the sessions that pad; their records count
+    by their padded inner plaintext."""
     lengths = np.asarray(lengths)
     sessions = np.asarray(sessions)
     short_max = 992 if seal else 992 + 8 + 16
     if tls13:
         short_max = 991 if seal else 992 + 16
+        if seal and pad_blocks:
+            lengths = np.asarray([tls13_inner_len(int(n), pad_blocks.get(int(s), 0)) - 1
+                                  for n, s in zip(lengths, sessions)])
     h = 0
     if len(lengths) and int(lengths.min()) > short_max:
         h |= HINT_NO_SHORT_RECORDS
@@ -500,10 +517,14 @@ def seal_wire(table: SessionTable, d_streams: int, n_streams: int, d_data: int, 
 
 
 def seal_wire_size(aead: int, data_len: int, max_fragment: int = 0, tag_len: int = 0,
-                   version: int | None = None) -> int:
+                   version: int | None = None, pad_block: int = 0) -> int:
     """Wire bytes of one tlsgpu_seal_wire stream; version=0x0304: TLS 1.3 framing
     (tlsgpu_seal_wire_size_v).  CHACHA20_POLY1305_TLS13 has that framing with
-    any version and with none."""
+    any version and with none.  pad_block: the session's TLS 1.3 padding block
+    (tlsgpu_seal_wire_size_p; needs the version)."""
+    if pad_block > 1 and version is not None:
+        return int(load_library().tlsgpu_seal_wire_size_p(aead, version, data_len, max_fragment,
+                                                          tag_len, pad_block))
     if version is None:
         return int(load_library().tlsgpu_seal_wire_size(aead, data_len, max_fragment, tag_len))
     return int(load_library().tlsgpu_seal_wire_size_v(aead, version, data_len, max_fragment,

@@ -14,7 +14,7 @@ from __future__ import annotations
 import numpy as np
 
 from . import (EXPLICIT_NONCE_LEN, RECORD_DTYPE, TAG_LEN, DeviceBuffer, SessionTable, len_type,
-               open_batch, seal_batch)
+               open_batch, seal_batch, tls13_inner_len)
 
 
 def _align(v: int, a: int, rem: int = 0) -> int:
@@ -34,11 +34,13 @@ class RecordBatch:
     type + tag (``content_type`` is the inner type) and an open's the whole
     inner plaintext, fragment - tag; the entries' kinds may be the TLS 1.3
     AES-GCM kinds and CHACHA20_POLY1305_TLS13, mixed.  The default is the
-    TLS 1.2 layout.
+    TLS 1.2 layout.  ``pad_blocks`` (a TLS 1.3 seal): {session_id: pad_block} of
+    the sessions installed with a padding block, so that ``out_lens`` and the
+    slot spacing use the padded fragment.
     """
 
     def __init__(self, engine, entries, mode: str, in_shift: int = 0, out_shift: int = 0,
-                 in_place: bool = False, tls13: bool = False):
+                 in_place: bool = False, tls13: bool = False, pad_blocks=None):
         assert mode in ("seal", "open")
         self.mode = mode
         n = len(entries)
@@ -50,7 +52,9 @@ class RecordBatch:
             ish = in_shift[i] if isinstance(in_shift, (list, tuple)) else in_shift
             if mode == "seal":
                 ip = _align(ip, 16) + ish
-                olen = len(payload) + eiv + (1 if tls13 else 0) + TAG_LEN
+                inner = (tls13_inner_len(len(payload), (pad_blocks or {}).get(sid, 0)) if tls13
+                         else len(payload))
+                olen = inner + eiv + TAG_LEN
                 op = _align(op, 16, (16 - eiv) % 16) + out_shift
             else:
                 ip = _align(ip, 16, (16 - eiv) % 16) + ish

@@ -203,6 +203,7 @@ struct PlanInput {
   int num_cus;
   bool have[kKinds];  // kind k is installed AND in the caller's kinds mask
   int generation;     // of the table: 12 / 13
+  bool cc_padded;     // the table holds a TLS 1.3 ChaCha session with a padding block
   bool seal, raw;
   bool bounds;        // a caller's batch: {in_bytes, out_bytes} to check against
   uint64_t in_bytes, out_bytes;
@@ -268,6 +269,7 @@ static BatchPlan plan_batch(const PlanInput& in) {
   const bool t13 = !in.raw && in.generation == 13;
   p.args.tls13 = t13 ? 1u : 0u;  // the launchers forward to the TLS 1.3 kernels and the unpad pass
   p.type_out = t13 && !in.seal && in.type_out;
+  p.args.cc_pad = t13 && in.seal && in.cc_padded ? 1u : 0u;  // launch_chacha: the PAD kernel
   p.args.bs16_min = t13 ? 0u : k.bs16_min;
   p.args.bs_reserve = k.bs_reserve;
   // batch-shape hints rule out the kernels the device would not select
@@ -481,7 +483,7 @@ int tg::run_batch(tlsgpu_sessions* t, const void* d_descs, uint32_t n, const uin
                   uint8_t* d_out, int32_t* d_status, hipStream_t s, bool seal, bool raw,
                   const Bounds* bounds, unsigned kinds, unsigned hints, tlsgpu_record* type_out) {
   const BatchKnobs& k = knobs();
-  PlanInput in = {n, t->eng->num_cus, {}, t->generation, seal, raw, bounds != nullptr,
+  PlanInput in = {n, t->eng->num_cus, {}, t->generation, t->cc_padded, seal, raw, bounds != nullptr,
                   bounds ? bounds->in_bytes : 0, bounds ? bounds->out_bytes : 0,
                   type_out != nullptr,
                   hints == ~0u ? t->hints.load(std::memory_order_relaxed) : hints,

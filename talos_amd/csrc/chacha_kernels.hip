@@ -294,7 +294,17 @@ __device__ __forceinline__ void cc_block_sk(uint32_t x[16], cu32c* k, uint32_t c
 // key stream.  When n - 1 is a multiple of 16, 64 or 128 the type byte is alone
 // in a new piece, block or step, and that step's gather loads nothing for the
 // record.  A step that does not hold the type byte pays one compare.
-template <bool SEAL, bool LATE_STORES, bool NARROW, bool UKEY = false, bool T13 = false>
+// PAD (T13 seal only): the table holds a session with a padding block (RFC 8446
+// 5.4), n = content || type || zeros.  A flag of its own, so tables without
+// padding run the instantiations they ran before.  The type's register carries
+// type | pad << 8 (pad <= 16383).  The gather's load predicate runs over the
+// content, n - 1 - pad of the source record's lane (one more shuffle per
+// piece), and zeroes in registers what a 16-B load brought in past the content:
+// those bytes lie inside the record now, where no last-piece mask drops them.
+// Pieces wholly past the content gather as zeros, and the step that holds
+// offset n - 1 - pad writes the type there.
+template <bool SEAL, bool LATE_STORES, bool NARROW, bool UKEY = false, bool T13 = false,
+          bool PAD = false>
 __device__ __forceinline__ void cc_tls_body(const BatchArgs& a, uint32_t r, uint32_t lane, uint8_t* tile,
                                             uint8_t* key, cu32c* ukey, bool active, uint32_t n,
                                             uint32_t tag_len_or_type,
@@ -302,6 +312,7 @@ __device__ __forceinline__ void cc_tls_body(const BatchArgs& a, uint32_t r, uint
                                             uint64_t src_v, uint64_t dst_v, Poly& p) {
   // T13: the tag is 16 bytes, and the register that carries a TLS 1.2 record's
   // tag length carries a seal's inner content type instead (none to spare)
+  static_assert(!PAD || (T13 && SEAL), "PAD is a TLS 1.3 seal instantiation");
   const uint32_t tag_len = T13 ? 16u : tag_len_or_type;
   // src_v / dst_v: the record's pointers, or with NARROW its 32-bit offsets in
   // the caller's buffers (an active record lies inside them, each at most
@@ -326,6 +337,8 @@ __device__ __forceinline__ void cc_tls_body(const BatchArgs& a, uint32_t r, uint
       const uint32_t off = base + 16u * (((lane % kCcP) - (rr >> 1)) & 7u);
       uint32_t snk = __shfl(n, (int)rr);
       if (T13 && SEAL) snk -= min(snk, 1u);  // the source: the content (an active n >= 1)
+      // ... without the padding (an inactive lane's register holds a tag length: pad 0)
+      if (PAD) snk -= (uint32_t)__shfl((int)tag_len_or_type, (int)rr) >> 8;
       // ds_bpermute outside the branch: an inactive source lane reads as 0
       const uint64_t srck = ptr_of(src_v, a.in, rr);
       v[k] = make_uint4(0, 0, 0, 0);
@@ -336,6 +349,16 @@ __device__ __forceinline__ void cc_tls_body(const BatchArgs& a, uint32_t r, uint
         } else {  // wire fragments (misaligned): only dwords that hold a record byte
           uint32_t w[4];
           load16_upto(sp, min(16u, snk - off), w);
+          v[k] = make_uint4(w[0], w[1], w[2], w[3]);
+        }
+        if (PAD && off + 16u > snk) {  // the content's last piece: zeros past the content
+          const uint32_t nbk = snk - off;  // 1..15
+          uint32_t w[4] = {v[k].x, v[k].y, v[k].z, v[k].w};
+#pragma unroll
+          for (int q = 0; q < 4; q++) {
+            const int32_t b = (int32_t)nbk - 4 * q;
+            w[q] &= b >= 4 ? 0xFFFFFFFFu : (b <= 0 ? 0u : ((1u << (8 * b)) - 1u));
+          }
           v[k] = make_uint4(w[0], w[1], w[2], w[3]);
         }
       }
@@ -370,9 +393,15 @@ __device__ __forceinline__ void cc_tls_body(const BatchArgs& a, uint32_t r, uint
     // loop below and its register peak are the TLS 1.2 ones).  One byte store:
     // what the gather left at and after offset n - 1 of that piece lies at or
     // past n and is masked below as in every last piece
-    if (T13 && SEAL && base < n && n - base <= kCcStep) {
+    if (T13 && SEAL && !PAD && base < n && n - base <= kCcStep) {
       const uint32_t tb = n - 1 - base;  // 0..127
       tile[cc_slot(lane, tb >> 4) + (tb & 15u)] = (uint8_t)tag_len_or_type;  // the lane's own row
+    }
+    // PAD: the step that holds offset n - 1 - pad, the content's length; the
+    // gather zeroed what follows it in the row
+    if (PAD && n != 0) {
+      const uint32_t tb = n - 1u - (tag_len_or_type >> 8) - base;  // wraps below base
+      if (tb < kCcStep) tile[cc_slot(lane, tb >> 4) + (tb & 15u)] = (uint8_t)tag_len_or_type;
     }
     // en/decrypt + MAC this lane's row: 2 ChaCha blocks
     if (base < n && !(a.hy_flags & kCcDiagNoCompute)) {
@@ -487,8 +516,9 @@ __device__ __forceinline__ void cc_tls_body(const BatchArgs& a, uint32_t r, uint
 
 // T13: records of TLSGPU_CHACHA20_POLY1305_TLS13 sessions only, in the TLS 1.3
 // layout (cc_tls_body); n = len + 1 on seal, len - 16 on open (the unpad pass
-// turns the open's status n into the content length afterwards).
-template <bool SEAL, bool LATE_STORES, bool NARROW = false, bool T13 = false>
+// turns the open's status n into the content length afterwards).  PAD: a seal's
+// n is the padded inner plaintext of the record's session (tls13_inner_len).
+template <bool SEAL, bool LATE_STORES, bool NARROW = false, bool T13 = false, bool PAD = false>
 __device__ void cc_tls_wave(const BatchArgs& a, uint32_t r, uint32_t lane, uint8_t* tile,
                             uint8_t* keys) {
   // --- parse (the fields the end of the record needs are re-derived there)
@@ -513,8 +543,11 @@ __device__ void cc_tls_wave(const BatchArgs& a, uint32_t r, uint32_t lane, uint8
       if (a.fused) {
         const uint64_t len = d.len_type & 0xFFFFFFu, tag = S->tag_len;
         const uint64_t eiv = S->nonce_in_record ? 8u : 0u;
-        // a TLS 1.3 seal writes content || type || tag (check_record_bounds's spans)
-        const uint64_t extra = T13 && kind == TLSGPU_CHACHA20_POLY1305_TLS13 ? 1u : 0u;
+        // a TLS 1.3 seal writes content || type || padding || tag (check_record_bounds's spans)
+        const uint64_t extra =
+            T13 && kind == TLSGPU_CHACHA20_POLY1305_TLS13
+                ? (PAD ? tls13_inner_len((uint32_t)len, S->pad_mask) - len : 1u)
+                : 0u;
         const uint64_t out_len =
             SEAL ? len + eiv + extra + tag : (len >= eiv + tag ? len - eiv - tag : 0);
         in_bounds = !(d.in_off > a.in_bytes || len > a.in_bytes - d.in_off ||
@@ -530,8 +563,9 @@ __device__ void cc_tls_wave(const BatchArgs& a, uint32_t r, uint32_t lane, uint8
         } else {
           active = true;
           sess = d.session;
-          n = SEAL ? len + (T13 ? 1u : 0u) : len - tag_len;
+          n = SEAL ? (PAD ? tls13_inner_len(len, S->pad_mask) : len + (T13 ? 1u : 0u)) : len - tag_len;
           if (T13) tag_len = type;  // cc_tls_body: the tag is 16 bytes, this is the type
+          if (PAD) tag_len |= (n - 1u - len) << 8;  // ... and the padding's length above it
           src = a.in + d.in_off;
           dst = a.out + d.out_off;
           // nonce: RFC 7905 fixed(12) XOR (0^4 || seq)
@@ -577,11 +611,11 @@ __device__ void cc_tls_wave(const BatchArgs& a, uint32_t r, uint32_t lane, uint8
                     !(a.hy_flags & kCcNoUkey);
   if (ukey) {
     cu32c* k = (cu32c*)(const uint32_t*)a.sessions[sid0].chacha_key;
-    cc_tls_body<SEAL, LATE_STORES, NARROW, true, T13>(a, r, lane, tile, key, k, active, n, tag_len,
-                                                      c13, c14, c15, sv, dv, p);
+    cc_tls_body<SEAL, LATE_STORES, NARROW, true, T13, PAD>(a, r, lane, tile, key, k, active, n,
+                                                           tag_len, c13, c14, c15, sv, dv, p);
   } else {
-    cc_tls_body<SEAL, LATE_STORES, NARROW, false, T13>(a, r, lane, tile, key, nullptr, active, n,
-                                                       tag_len, c13, c14, c15, sv, dv, p);
+    cc_tls_body<SEAL, LATE_STORES, NARROW, false, T13, PAD>(a, r, lane, tile, key, nullptr, active,
+                                                            n, tag_len, c13, c14, c15, sv, dv, p);
   }
 }
 
@@ -690,25 +724,26 @@ __device__ __forceinline__ void cc_parse_raw(const RawJob& j, const DevSession* 
 }
 
 // TLS batches: LDS-staged coalesced data path (cc_tls_wave), 4 waves per SIMD.
-// T13 (this kernel and chacha_tls_kernel): the instantiation a TLS 1.3 table runs.
-template <bool SEAL, bool T13 = false>
+// T13 (this kernel and chacha_tls_kernel): the instantiation a TLS 1.3 table runs;
+// PAD: a seal on a TLS 1.3 table that holds a ChaCha session with a padding block.
+template <bool SEAL, bool T13 = false, bool PAD = false>
 __global__ __launch_bounds__(kCcThreads) void chacha_tls_wide_kernel(BatchArgs a) {
   __shared__ __attribute__((aligned(16))) uint8_t tiles[kCcThreads / kWave][kCcTile];
   __shared__ __attribute__((aligned(16))) uint8_t keys[kCcThreads / kWave][kCcKeys];
   const uint32_t lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  cc_tls_wave<SEAL, false, false, T13>(a, blockIdx.x * blockDim.x + threadIdx.x, lane, tiles[wave],
-                                       keys[wave]);
+  cc_tls_wave<SEAL, false, false, T13, PAD>(a, blockIdx.x * blockDim.x + threadIdx.x, lane,
+                                            tiles[wave], keys[wave]);
 }
 // the same with 32-bit pointer shuffles (NARROW: cc_tls_body) — what a fused
 // batch (bounds known, buffers of at most 4 GiB) runs: C +0.6 %
 // (profiles/r05ap_ab_cc_narrow.txt); 64-bit shuffles otherwise
-template <bool SEAL, bool T13 = false>
+template <bool SEAL, bool T13 = false, bool PAD = false>
 __global__ __launch_bounds__(kCcThreads) void chacha_tls_kernel(BatchArgs a) {
   __shared__ __attribute__((aligned(16))) uint8_t tiles[kCcThreads / kWave][kCcTile];
   __shared__ __attribute__((aligned(16))) uint8_t keys[kCcThreads / kWave][kCcKeys];
   const uint32_t lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  cc_tls_wave<SEAL, false, true, T13>(a, blockIdx.x * blockDim.x + threadIdx.x, lane, tiles[wave],
-                                      keys[wave]);
+  cc_tls_wave<SEAL, false, true, T13, PAD>(a, blockIdx.x * blockDim.x + threadIdx.x, lane,
+                                           tiles[wave], keys[wave]);
 }
 // the LATE_STORES order (A/B only, TLSGPU_CC_ORDER): at 3 waves per SIMD (131
 // VGPRs), and held to 128 VGPRs (4 waves per SIMD, 5 spilled)
@@ -835,8 +870,14 @@ int launch_chacha(const BatchArgs& a, bool seal, bool raw, bool rfc, bool old, h
     if (!rfc) return 0;
     BatchArgs b = a;
     b.hy_flags = 0;
-    if (narrow_ok) hipLaunchKernelGGL(CC_DIR(chacha_tls_kernel, true), grid, block, 0, s, b);
-    else hipLaunchKernelGGL(CC_DIR(chacha_tls_wide_kernel, true), grid, block, 0, s, b);
+    if (seal && a.cc_pad) {  // a session of the table pads its records: the PAD instantiation
+      if (narrow_ok) hipLaunchKernelGGL((chacha_tls_kernel<true, true, true>), grid, block, 0, s, b);
+      else hipLaunchKernelGGL((chacha_tls_wide_kernel<true, true, true>), grid, block, 0, s, b);
+    } else if (narrow_ok) {
+      hipLaunchKernelGGL(CC_DIR(chacha_tls_kernel, true), grid, block, 0, s, b);
+    } else {
+      hipLaunchKernelGGL(CC_DIR(chacha_tls_wide_kernel, true), grid, block, 0, s, b);
+    }
     if (hipGetLastError() != hipSuccess) return -1;
     return seal ? 0 : launch_tls13_unpad(a, 0, s);
   }

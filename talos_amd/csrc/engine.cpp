@@ -93,6 +93,7 @@ extern "C" int tlsgpu_sessions_create(tlsgpu_engine* e, uint32_t capacity, tlsgp
   t->capacity = capacity;
   t->kinds.assign(capacity, 0);
   t->tag_lens.assign(capacity, 16);
+  t->pad_masks.assign(capacity, 0);
   t->owners.assign(capacity, nullptr);
   memset(t->have, 0, sizeof(t->have));
   if (hipMalloc(&t->d_sess, sizeof(DevSession) * (size_t)capacity) != hipSuccess ||
@@ -133,6 +134,11 @@ bool tg::valid_params(const tlsgpu_session_params& p) {
     return false;
   // ... and that kind exists in TLS 1.3 only
   if (p.aead == TLSGPU_CHACHA20_POLY1305_TLS13 && p.version != kTls13Version) return false;
+  // the TLS 1.3 padding block (read for that version only): none, or a power of
+  // two up to 16384 (tls13_inner_len rounds with a mask)
+  if (p.version == kTls13Version && p.pad_block > 1 &&
+      (p.pad_block > 16384 || (p.pad_block & (p.pad_block - 1)) != 0))
+    return false;
   switch (p.aead) {
     case TLSGPU_AES_128_GCM: return p.key_len == 16;
     case TLSGPU_AES_256_GCM:
@@ -185,6 +191,9 @@ extern "C" int tlsgpu_sessions_install(tlsgpu_sessions* t, uint32_t first, uint3
   for (uint32_t i = 0; i < n; i++) {
     t->kinds[first + i] = params[i].aead;
     t->tag_lens[first + i] = (uint8_t)(params[i].tag_len ? params[i].tag_len : 16);
+    t->pad_masks[first + i] = (uint16_t)tls13_pad_mask(params[i].version, params[i].pad_block);
+    if (params[i].aead == TLSGPU_CHACHA20_POLY1305_TLS13 && t->pad_masks[first + i])
+      t->cc_padded = true;
     t->have[params[i].aead] = true;
   }
   return TLSGPU_OK;

@@ -644,9 +644,12 @@ struct RecCtx {
                           // time so the tag check never waits on HBM
   uint8_t* tag_out;       // seal: where the tag goes
   uint32_t n;             // plaintext length (TLS 1.3: the inner plaintext, content || type)
-  uint32_t inner;         // 0, or 0x100 | inner content type for a TLS 1.3 seal: src holds
-                          // n - 1 content bytes and byte n - 1 is this type (RFC 8446 5.2);
-                          // src is never read past the content
+  uint32_t inner;         // 0, or for a TLS 1.3 seal 0x100 | inner content type | the source
+                          // length << 9: src holds that many content bytes, counted from
+                          // the record's start (< 2^20, TLSGPU_MAX_RECORD), the byte after
+                          // them is this type and zeros follow up to n (RFC 8446 5.2,
+                          // 5.4); src is never read past the content.  One word, so the
+                          // context is the TLS 1.2 kernels' and no wider than it was
   uint32_t j0[4];         // J0 (LE words)
   uint32_t aad_be[4];     // AAD' = Horner of the AAD blocks without the final
                           // multiply (gcm128.c:826-881 folded), BE words
@@ -655,29 +658,32 @@ struct RecCtx {
   int32_t ok_status;      // status written on success
 };
 
-// Bytes of the record that come from rc.src: all of them, or all but a TLS 1.3
-// seal's synthesized type byte.  The wide full-step loops count their steps
-// over these, so the block that holds the type byte always takes a tail path
-// (load_tail) and the step loops load 16 source bytes per block as before.
+// Bytes of the record that come from rc.src: all of them, or a TLS 1.3 seal's
+// content (the type byte and the padding are synthesized).  The wide full-step
+// loops count their steps over these, so the block that holds the type byte and
+// the padding blocks always take a tail path (load_tail) and the step loops
+// load 16 source bytes per block as before.  (min: the split kernel's context
+// of a wave's range ends at rc.n, the source maybe later.)
 __device__ __forceinline__ uint32_t src_bytes(const RecCtx& rc) {
-  if constexpr (kTls13) return rc.n - (rc.inner >> 8);
+  if constexpr (kTls13) return rc.inner ? min(rc.inner >> 9, rc.n) : rc.n;
   return rc.n;
 }
 
 // Block i of the record's input for the tail paths, `nbytes` (0..16) of it
 // valid: load_block of the bytes that src holds, then a TLS 1.3 seal's inner
-// content type at byte n - 1.  A block that holds the type byte alone loads
-// nothing.
+// content type in the one block that holds offset src_len.  A block that holds
+// the type byte alone, and every padding block past it, loads nothing and is
+// zero (a padding block's ciphertext is the key stream).
 template <bool SEAL>
 __device__ __forceinline__ void load_tail(const RecCtx& rc, uint32_t i, uint32_t nbytes,
                                           bool aligned, uint32_t v[4]) {
   if constexpr (!SEAL || !kTls13) {
     load_block(rc.src + 16u * i, nbytes, aligned, v);
   } else {
-    const uint32_t ns = src_bytes(rc), off = 16u * i;
+    const uint32_t ns = rc.inner ? rc.inner >> 9 : rc.n, off = 16u * i;  // the source length
     const uint32_t lb = min(nbytes, ns > off ? ns - off : 0u);
     load_block(rc.src + off, lb, aligned, v);
-    if (lb != nbytes) {  // the type byte is byte lb of this block
+    if (rc.inner != 0 && (ns >> 4) == i && nbytes != 0) {  // the type byte is byte lb of this block
       const uint32_t t = (rc.inner & 0xFFu) << (8u * (lb & 3u));
 #pragma unroll
       for (uint32_t w = 0; w < 4; w++) v[w] |= (lb >> 2) == w ? t : 0u;
@@ -1295,8 +1301,12 @@ __device__ __forceinline__ bool parse_tls(const tlsgpu_record& d, const DevSessi
   uint32_t tag_len = as_const(&S->tag_len)[0];
   const bool t13 = gcm_tls13(S);
   const uint32_t eiv = t13 ? 0u : 8u;      // explicit nonce in the fragment
-  const uint32_t extra = t13 ? 1u : 0u;    // seal: the synthesized type byte
-  if (SEAL ? len > TLSGPU_MAX_RECORD - extra
+  // seal: the synthesized type byte and the session's padding (tls13_inner_len;
+  // a record longer than 16384 is never padded, so the bound is the type byte's)
+  uint32_t extra = 0;
+  if constexpr (kTls13)
+    extra = SEAL ? tls13_inner_len(len, as_const(&S->pad_mask)[0]) - len : 0u;
+  if (SEAL ? len > TLSGPU_MAX_RECORD - (t13 ? 1u : 0u)
            : (len < eiv || len - eiv < tag_len || len - eiv - tag_len > TLSGPU_MAX_RECORD)) {
     if (lane == 0) *status_slot = TLSGPU_REC_PUBLIC_INVALID;
     return false;
@@ -1304,7 +1314,7 @@ __device__ __forceinline__ bool parse_tls(const tlsgpu_record& d, const DevSessi
   uint32_t e1, e2;  // nonce words 1, 2
   if (SEAL) {
     rc.n = len + extra;
-    rc.inner = t13 ? 0x100u | type : 0u;
+    rc.inner = t13 ? 0x100u | type | (len << 9) : 0u;
     rc.src = ip;
     rc.dst = op + eiv;
     rc.tag_out = op + eiv + rc.n;

@@ -306,10 +306,13 @@ namespace tg {
 __device__ __forceinline__ bool rec_in_bounds(const tlsgpu_record& d, const DevSession* S,
                                               uint64_t in_bytes, uint64_t out_bytes, bool seal) {
   const uint64_t eiv = as_const(&S->nonce_in_record)[0] ? 8u : 0u, tag = as_const(&S->tag_len)[0];
-  // a TLS 1.3 seal writes content || type || tag
-  uint64_t extra = 0;
-  if constexpr (kTls13) extra = is_gcm(as_const(&S->kind)[0]) ? 1u : 0u;
+  // a TLS 1.3 seal writes content || type || padding || tag
   const uint64_t len = d.len_type & 0xFFFFFFu;
+  uint64_t extra = 0;
+  if constexpr (kTls13)
+    extra = is_gcm(as_const(&S->kind)[0])
+                ? tls13_inner_len((uint32_t)len, as_const(&S->pad_mask)[0]) - len
+                : 0u;
   const uint64_t out_len = seal ? len + eiv + extra + tag : (len >= eiv + tag ? len - eiv - tag : 0);
   return !(d.in_off > in_bytes || len > in_bytes - d.in_off || d.out_off > out_bytes ||
            out_len > out_bytes - d.out_off);
@@ -416,12 +419,15 @@ constexpr uint32_t kPackNone = 0xFFu;
 // Lanes record descriptor word len_type needs in a pack, or kPackNone when it
 // takes the single-record path (too long, or publicly invalid: parse_tls).
 // eiv: the session's explicit nonce length, 8 (TLS 1.2) or 0 (TLS 1.3, whose
-// seal also appends the type byte): nb counts blocks of inner plaintext.
+// seal also appends the type byte and the padding of the session's pad_mask):
+// nb counts blocks of the padded inner plaintext, so a session with a padding
+// block of 1024 or more never packs.
 template <bool SEAL>
-__device__ __forceinline__ uint32_t pack_need(uint32_t len_type, uint32_t tag_len, uint32_t eiv) {
+__device__ __forceinline__ uint32_t pack_need(uint32_t len_type, uint32_t tag_len, uint32_t eiv,
+                                              uint32_t pad_mask) {
   const uint32_t len = len_type & 0xFFFFFFu;
   if (!SEAL && len < eiv + tag_len) return kPackNone;
-  const uint32_t n = SEAL ? len + (eiv ? 0u : 1u) : len - eiv - tag_len;
+  const uint32_t n = SEAL ? (eiv ? len : tls13_inner_len(len, pad_mask)) : len - eiv - tag_len;
   const uint32_t nb = (n + 15) >> 4;
   return nb + 2 <= kPackMaxNeed ? nb + 2 : kPackNone;
 }
@@ -467,7 +473,8 @@ __device__ void gcm_pack(const BatchArgs& a, const RecPre* __restrict__ pre, uin
   const uint32_t len = d.len_type & 0xFFFFFFu;
   const uint8_t* ip = a.in + d.in_off;
   uint8_t* op = a.out + d.out_off;
-  const uint32_t n = SEAL ? len + (t13 ? 1u : 0u) : len - eiv - tag_len;
+  const uint32_t n = SEAL ? (t13 ? tls13_inner_len(len, as_const(&S->pad_mask)[0]) : len)
+                          : len - eiv - tag_len;
   const uint8_t* src = SEAL ? ip : ip + eiv;
   uint8_t* dst = SEAL ? op + eiv : op;
   const uint4* P = reinterpret_cast<const uint4*>(pre + r);
@@ -483,11 +490,12 @@ __device__ void gcm_pack(const BatchArgs& a, const RecPre* __restrict__ pre, uin
   const uint32_t nbytes = blk ? min(16u, n - 16u * jb) : 0u;
   const bool aligned = ((((uintptr_t)(src + 16u * jb)) | ((uintptr_t)(dst + 16u * jb))) & 15) == 0;
   uint32_t in[4] = {0, 0, 0, 0}, ks[4];
-  // a TLS 1.3 seal: the last block's last byte is the inner content type, not
-  // read from src (load_tail, gcm_device.h)
+  // a TLS 1.3 seal: the block that holds offset len takes the inner content
+  // type there, not read from src, and the blocks past it are padding and load
+  // nothing (load_tail, gcm_device.h)
   const uint32_t lbytes = SEAL && t13 ? min(nbytes, len - min(len, 16u * jb)) : nbytes;
   if (blk) load_block(src + 16u * jb, lbytes, aligned, in);
-  if (SEAL && lbytes != nbytes) {
+  if (SEAL && t13 && blk && (len >> 4) == jb) {
     const uint32_t t = (d.len_type >> 24) << (8u * (lbytes & 3u));
 #pragma unroll
     for (uint32_t w = 0; w < 4; w++) in[w] |= (lbytes >> 2) == w ? t : 0u;
@@ -967,7 +975,9 @@ __global__ __launch_bounds__(NT, 1) void TG_GEN(gcm_hy_kernel)(BatchArgs a,
     const uint32_t tag_len = as_const(&S->tag_len)[0];
     constexpr uint32_t eiv = kTls13 ? 0u : 8u;
     const uint32_t run_cap = packing ? min(rhi, pos + kPlanCap) : rhi;
-    bool has_short = packing && pack_need<SEAL>(as_const(&D[pos].len_type)[0], tag_len, eiv) <= kPackMaxNeed;
+    const uint32_t pad_mask = kTls13 && packing ? as_const(&S->pad_mask)[0] : 0u;
+    bool has_short = packing &&
+                     pack_need<SEAL>(as_const(&D[pos].len_type)[0], tag_len, eiv, pad_mask) <= kPackMaxNeed;
     uint32_t run_end = pos + 1;
     // the run's end: 4 x 64 descriptors per memory round trip (the scan is
     // on the run-to-run critical path of the wave that finished last; round 5,
@@ -987,7 +997,7 @@ __global__ __launch_bounds__(NT, 1) void TG_GEN(gcm_hy_kernel)(BatchArgs a,
         const uint32_t p = run_end + 64u * u + lane;
         if (packing)  // a hint only: records past the run's end may count
           has_short |= __ballot(p < run_cap && s[u] == sid &&
-                                pack_need<SEAL>(lt[u], tag_len, eiv) <= kPackMaxNeed) != 0;
+                                pack_need<SEAL>(lt[u], tag_len, eiv, pad_mask) <= kPackMaxNeed) != 0;
         const uint64_t diff = __ballot(p < run_cap && s[u] != sid);
         if (diff && found == 0xFFFFFFFFu)
           found = 64u * u + __builtin_amdgcn_readfirstlane((uint32_t)__builtin_ctzll(diff));
@@ -1013,7 +1023,8 @@ __global__ __launch_bounds__(NT, 1) void TG_GEN(gcm_hy_kernel)(BatchArgs a,
         __syncthreads();
         for (uint32_t c = wave * kWave; c < run_len; c += NT) {  // ballot compaction per wave
           const uint32_t t = c + lane;
-          const uint32_t nd = t < run_len ? pack_need<SEAL>(D[pos + t].len_type, tag_len, eiv) : 0u;
+          const uint32_t nd =
+              t < run_len ? pack_need<SEAL>(D[pos + t].len_type, tag_len, eiv, pad_mask) : 0u;
           // fused: an out-of-bounds record takes the long-record path, which
           // skips it (its status was written by the prologue)
           const bool sh = t < run_len && nd <= kPackMaxNeed &&
@@ -1187,8 +1198,8 @@ __global__ __launch_bounds__(kPrepThreads) void TG_GEN(gcm_prep_kernel)(BatchArg
       S = a.sessions + d.session;
       mine = is_gcm(S->kind) && (int)S->rounds == ROUNDS;
       run_start = mine && (r == 0 || D[r - 1].session != d.session);
-      packable = mine && pack_need<SEAL>(d.len_type, S->tag_len, kTls13 ? 0u : 8u) <=
-                             kPackMaxNeed;
+      packable = mine && pack_need<SEAL>(d.len_type, S->tag_len, kTls13 ? 0u : 8u,
+                                         kTls13 ? S->pad_mask : 0u) <= kPackMaxNeed;
     }
   }
   // selection words (a.sel, SelSums): summed per wave (ballot), per workgroup

@@ -128,8 +128,10 @@ __device__ __forceinline__ bool gcm_raw_job(const BatchArgs& a, uint32_t r,
     } else {
       RecCtx part = rc;
       const uint32_t e1 = s0 + spw * kWave;  // full blocks only
+      // (a TLS 1.3 seal: part keeps the source length, counted from the record's
+      // start, and the type, so load_tail sees where the content ends relative to
+      // this range's blocks; with padding it can end in any wave's range)
       part.n = 16u * e1;
-      part.inner = 0;  // a TLS 1.3 seal's type byte lies in the last range
       gcm_blocks<SEAL, ROUNDS, false>(part, S, none, cc, x, s0, lane, laneoff, gl);
       TG_JOB_MARK(3);
       e = nb + 1 - (e1 - kWave + lane);

@@ -62,6 +62,9 @@ struct tlsgpu_sessions {
   tg::DevGcmTables* d_gcm;
   std::vector<int32_t> kinds;  // host mirror of installed kinds
   std::vector<uint8_t> tag_lens;  // and tag lengths (host pipeline output spans)
+  std::vector<uint16_t> pad_masks;  // and TLS 1.3 padding masks (DevSession::pad_mask: spans, hints)
+  bool cc_padded = false;      // a TLS 1.3 ChaCha session with a padding block was installed
+                               // (BatchArgs::cc_pad; never cleared: the PAD kernel runs any table)
   std::vector<const void*> owners;  // SSL* per session for the TaLoS hooks (set_owner)
   int generation = 0;          // 0: nothing installed yet; 12 / 13: every session is TLS <= 1.2 /
                                // TLS 1.3 (version 0x0304, RFC 8446 record layout) — set by

@@ -40,14 +40,20 @@ static const long g_host_fail_chunk = [] {
 // record short enough for a pack (GCM n <= 992 B, the open length with the
 // explicit nonce and the longest tag), and session runs long enough for the
 // run-at-a-time queue kernel (pws_selected: runs * kPwsRun <= records).  A
-// TLS 1.3 table: 62 blocks of inner plaintext, i.e. 991 B of content on seal
-// (the type byte follows it) and 992 B + the tag on open (no explicit nonce).
-static unsigned host_hints(const tlsgpu_record* r, uint32_t n, bool seal, bool t13) {
-  const uint32_t short_max = t13 ? (seal ? 991u : 992u + 16u) : (seal ? 992u : 992u + 8u + 16u);
+// TLS 1.3 table: 62 blocks of inner plaintext, i.e. 992 B + the tag on open (no
+// explicit nonce) and on seal a padded inner plaintext (tls13_inner_len under
+// the session's padding mask) of at most 992 B: 991 B of content without a
+// padding block, none with a block of 1024 or more.
+static unsigned host_hints(const tlsgpu_sessions* t, const tlsgpu_record* r, uint32_t n, bool seal,
+                           bool t13) {
+  const uint32_t short_max = t13 ? (seal ? 992u : 992u + 16u) : (seal ? 992u : 992u + 8u + 16u);
   bool shorts = false;
   uint32_t runs = 0;
   for (uint32_t i = 0; i < n; i++) {
-    shorts |= (r[i].len_type & 0xFFFFFFu) <= short_max;
+    uint32_t len = r[i].len_type & 0xFFFFFFu;
+    if (t13 && seal)
+      len = tls13_inner_len(len, r[i].session < t->capacity ? t->pad_masks[r[i].session] : 0u);
+    shorts |= len <= short_max;
     runs += (i == 0 || r[i].session != r[i - 1].session) ? 1u : 0u;
   }
   return (shorts ? 0u : TLSGPU_HINT_NO_SHORT_RECORDS) |
@@ -106,8 +112,8 @@ static int host_batch(tlsgpu_sessions* t, bool seal, const tlsgpu_record* h_recs
   };
   // the output span exactly (open: the plaintext, explicit nonce and tag
   // excluded — for TLS 1.3 the whole inner plaintext, padding included; seal:
-  // the fragment, for TLS 1.3 content + type + tag): a neighbouring chunk's D2H
-  // on another stream may own the next byte
+  // the fragment, for TLS 1.3 the padded inner plaintext + tag): a neighbouring
+  // chunk's D2H on another stream may own the next byte
   const bool t13 = t->generation == 13;
   auto span_out = [&](const tlsgpu_record& r, uint64_t* lo, uint64_t* hi) {
     const uint64_t len = r.len_type & 0xFFFFFFu;
@@ -115,8 +121,10 @@ static int host_batch(tlsgpu_sessions* t, bool seal, const tlsgpu_record* h_recs
     if (r.session < t->capacity) {
       const int k = t->kinds[r.session];
       const bool gcm = k == TLSGPU_AES_128_GCM || k == TLSGPU_AES_256_GCM;
-      const bool s13 = tls13_session((uint32_t)k, t13 ? 0u : 1u);  // GCM or ChaCha: + the type byte
-      over = (gcm && !s13 ? 8 : 0) + (s13 && seal ? 1 : 0) + t->tag_lens[r.session];
+      const bool s13 = tls13_session((uint32_t)k, t13 ? 0u : 1u);  // GCM or ChaCha
+      // a TLS 1.3 seal: + the type byte and the session's padding
+      const uint64_t grow = s13 && seal ? tls13_inner_len((uint32_t)len, t->pad_masks[r.session]) - len : 0;
+      over = (gcm && !s13 ? 8 : 0) + grow + t->tag_lens[r.session];
     }
     *lo = std::min<uint64_t>(r.out_off, out_bytes);
     *hi = std::min<uint64_t>(r.out_off + (seal ? len + over : (len > over ? len - over : 0)),
@@ -194,7 +202,7 @@ static int host_batch(tlsgpu_sessions* t, bool seal, const tlsgpu_record* h_recs
       if (!in_place && ohi > olo) HIPCHK(hipMemsetAsync(d_out + olo, 0, ohi - olo, hs));
       const Bounds bd = {in_bytes, out_bytes};
       const int rc = run_batch(t, hp.d_recs + a, b - a, d_in, d_out, hp.d_status + a, hs, seal,
-                               false, &bd, ~0u, host_hints(h_recs + a, b - a, seal, t13));
+                               false, &bd, ~0u, host_hints(t, h_recs + a, b - a, seal, t13));
       if (rc != TLSGPU_OK) return rc;
       HIPCHK(hipEventRecord(ev_done, hs));
       HIPCHK(hipStreamWaitEvent(s_out, ev_done, 0));
@@ -381,13 +389,32 @@ extern "C" uint64_t tlsgpu_seal_wire_size(int aead, uint32_t data_len, uint32_t 
 
 extern "C" uint64_t tlsgpu_seal_wire_size_v(int aead, uint16_t version, uint32_t data_len,
                                             uint32_t max_fragment, uint32_t tag_len) {
+  return tlsgpu_seal_wire_size_p(aead, version, data_len, max_fragment, tag_len, 0);
+}
+
+extern "C" uint64_t tlsgpu_seal_wire_size_p(int aead, uint16_t version, uint32_t data_len,
+                                            uint32_t max_fragment, uint32_t tag_len,
+                                            uint32_t pad_block) {
   const bool gcm = aead == TLSGPU_AES_128_GCM || aead == TLSGPU_AES_256_GCM;
-  if (version != kTls13Version || !gcm)  // (the TLS 1.3 ChaCha kind: TLS 1.3 framing there too)
-    return tlsgpu_seal_wire_size(aead, data_len, max_fragment, tag_len);
-  // TLS 1.3: header(5) || content || inner type(1) || tag(16) per record, no explicit nonce
+  const bool cc13 = aead == TLSGPU_CHACHA20_POLY1305_TLS13;
+  // pad_block as an install reads it: TLS 1.3 sessions only, a power of two up to 16384
+  const bool padded = version == kTls13Version && (gcm || cc13) && pad_block > 1 &&
+                      pad_block <= 16384 && (pad_block & (pad_block - 1)) == 0;
+  if (!padded) {
+    if (version != kTls13Version || !gcm)  // (the TLS 1.3 ChaCha kind: TLS 1.3 framing there too)
+      return tlsgpu_seal_wire_size(aead, data_len, max_fragment, tag_len);
+    // TLS 1.3: header(5) || content || inner type(1) || tag(16) per record, no explicit nonce
+    const uint32_t frag = max_fragment == 0 || max_fragment > 16384 ? 16384 : max_fragment;
+    const uint64_t nrec = ((uint64_t)data_len + frag - 1) / frag;
+    return data_len + nrec * (5 + 1 + 16);
+  }
+  // header(5) || padded inner plaintext || tag(16): every record but the last
+  // holds frag bytes, the last the remainder
   const uint32_t frag = max_fragment == 0 || max_fragment > 16384 ? 16384 : max_fragment;
-  const uint64_t nrec = ((uint64_t)data_len + frag - 1) / frag;
-  return data_len + nrec * (5 + 1 + 16);
+  const uint32_t mask = pad_block - 1;
+  const uint64_t full = data_len / frag, rest = data_len % frag;
+  return full * (5 + (uint64_t)tls13_inner_len(frag, mask) + 16) +
+         (rest ? 5 + (uint64_t)tls13_inner_len((uint32_t)rest, mask) + 16 : 0);
 }
 
 extern "C" int tlsgpu_fill_synthetic(tlsgpu_engine* e, uint8_t* d_out, uint64_t stride,

@@ -199,6 +199,7 @@ bool host_session_image(const tlsgpu_session_params& p, DevSession* s, DevGcmTab
   s->xor_fixed_nonce = p.aead == TLSGPU_CHACHA20_POLY1305 || cc13;
   s->nonce_in_record = gcm && p.version != 0x0304;  // TLS 1.3: no explicit nonce
   s->version = p.version;
+  s->pad_mask = tls13_pad_mask(p.version, p.pad_block);
   memcpy(s->fixed_nonce, p.fixed_iv, p.fixed_iv_len);
   if (cc) memcpy(s->chacha_key, p.key, 32);
   if (!gcm) return false;

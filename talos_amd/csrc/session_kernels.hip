@@ -210,6 +210,7 @@ __device__ __forceinline__ void install_body(DevSession* __restrict__ sessions,
     s.xor_fixed_nonce = p.aead == TLSGPU_CHACHA20_POLY1305 || cc13;
     s.nonce_in_record = gcm && p.version != 0x0304;  // TLS 1.3: no explicit nonce
     s.version = p.version;
+    s.pad_mask = tls13_pad_mask(p.version, p.pad_block);  // a TLS 1.3 seal's padding block
     for (uint32_t k = 0; k < p.fixed_iv_len; k++) s.fixed_nonce[k] = p.fixed_iv[k];
     if (cc)
       for (int k = 0; k < 32; k++) s.chacha_key[k] = p.key[k];
@@ -361,9 +362,11 @@ __global__ void check_record_bounds(const tlsgpu_record* __restrict__ recs,
   if (r.session < n_sessions) {
     const DevSession& S = sessions[r.session];
     const uint64_t eiv = S.nonce_in_record ? 8u : 0u, tag = S.tag_len;
-    // a TLS 1.3 seal writes content || type || tag (RFC 8446 5.2)
-    const uint64_t extra = tls13_session(S.kind, S.nonce_in_record) ? 1u : 0u;
+    // a TLS 1.3 seal writes content || type || padding || tag (RFC 8446 5.2, 5.4)
     const uint64_t len = r.len_type & 0xFFFFFFu;
+    const uint64_t extra = tls13_session(S.kind, S.nonce_in_record)
+                               ? tls13_inner_len((uint32_t)len, S.pad_mask) - len
+                               : 0u;
     const uint64_t in_len = len;
     const uint64_t out_len =
         seal ? len + eiv + extra + tag : (len >= eiv + tag ? len - eiv - tag : 0);

@@ -32,7 +32,9 @@ struct alignas(16) DevSession {
   uint32_t h_le[4];           // H = E_K(0), little-endian words
   uint32_t rk_rot[60];        // rotr16(rk[i]): round keys pre-rotated for the
                               // xor3 + alignbit + xor3 column form
-  uint32_t reserved[112];
+  uint32_t pad_mask;          // TLS 1.3 seal padding: block - 1 (a power of two), 0 = none;
+                              // always 0 for a TLS 1.2 session (tls13_inner_len)
+  uint32_t reserved[111];
 };
 static_assert(sizeof(DevSession) == 1024, "DevSession layout");
 
@@ -44,6 +46,23 @@ static_assert(sizeof(DevSession) == 1024, "DevSession layout");
 __host__ __device__ __forceinline__ bool tls13_session(uint32_t kind, uint32_t nonce_in_record) {
   return kind == TLSGPU_CHACHA20_POLY1305_TLS13 ||
          ((kind == TLSGPU_AES_128_GCM || kind == TLSGPU_AES_256_GCM) && nonce_in_record == 0);
+}
+// Inner plaintext length of a TLS 1.3 seal of `len` content bytes (RFC 8446 5.4:
+// content || type || zeros): len + 1 rounded up to the session's padding block,
+// pad_mask = block - 1 (a power of two up to 16384) or 0.  A record beyond the
+// protocol's 16384 bytes (the engine's wider TLSGPU_MAX_RECORD range) is never
+// padded, so a padded inner plaintext is at most 16385 bytes.  The only place
+// the rule is written: every kernel and host path that sizes, bounds or frames a
+// TLS 1.3 seal asks here.
+__host__ __device__ __forceinline__ uint32_t tls13_inner_len(uint32_t len, uint32_t pad_mask) {
+  return len >= 16384u ? len + 1u : (len + 1u + pad_mask) & ~pad_mask;
+}
+// pad_mask of a session with params.pad_block = b: read for TLS 1.3 sessions
+// only; a power of two from 2 to 16384 is the block, and everything else (0, 1,
+// and what valid_params rejects at install) is no padding
+__host__ __device__ __forceinline__ uint32_t tls13_pad_mask(uint32_t version, uint32_t pad_block) {
+  const bool block = pad_block > 1u && pad_block <= 16384u && (pad_block & (pad_block - 1u)) == 0;
+  return version == 0x0304u && block ? pad_block - 1u : 0u;
 }
 // number of AEAD kinds + 1: arrays indexed by enum tlsgpu_aead
 constexpr int kKinds = TLSGPU_CHACHA20_POLY1305_TLS13 + 1;
@@ -241,6 +260,9 @@ struct BatchArgs {
   tlsgpu_record* type_out;          // TLS 1.3 open, non-null (tlsgpu_open_wire: the engine's own
                                     // descriptors): the unpad pass also moves every opened
                                     // record's inner content type into len_type's type bits
+  uint32_t cc_pad;                  // seal: the table holds a TLS 1.3 ChaCha session with a
+                                    // padding block (run_batch); launch_chacha then runs the
+                                    // staged kernel's PAD instantiation
 };
 
 // Work-balanced ranges (round 5): a record's work for the cut — its payload

@@ -415,13 +415,16 @@ __global__ __launch_bounds__(256) void wire_seal_frame_kernel(
   if (nrec) {
     const DevSession& S = sessions[st.session];
     // TLS 1.3 (tls13_session: GCM or ChaCha): the fragment is content || inner type ||
-    // tag under the header 17 03 03 (RFC 8446 5.2); st.type is the inner type
+    // padding || tag under the header 17 03 03 (RFC 8446 5.2, 5.4: the padded inner
+    // plaintext of tls13_inner_len, per record); st.type is the inner type
     const bool t13 = tls13_session(S.kind, S.nonce_in_record);
-    const uint32_t over = (S.nonce_in_record ? 8u : 0u) + (t13 ? 1u : 0u) + S.tag_len;  // eivlen + tag
+    const uint32_t pad_mask = S.pad_mask;
+    const uint32_t over = (S.nonce_in_record ? 8u : 0u) + S.tag_len;  // eivlen + tag
     uint64_t pos = st.wire_off;
     for (uint32_t k = 0; k < nrec; k++) {
       const uint32_t len = min(frag, st.data_len - k * frag);
-      const uint32_t L = len + over;  // the length field (s3_pkt.c:733)
+      // the length field (s3_pkt.c:733)
+      const uint32_t L = (t13 ? tls13_inner_len(len, pad_mask) : len) + over;
       if (pos <= wire_bytes && (uint64_t)kHdr + L <= wire_bytes - pos) {  // no wrap
         uint8_t* h = wire + pos;
         h[0] = t13 ? (uint8_t)kAppData : st.type;

@@ -25,6 +25,14 @@ Ciphersuites = SUITE) and starts itself as a fresh child process with
 OPENSSL_CONF pointing at it; still two MemoryBIOs, no socket.  The records are
 opened with the oracle's RFC 7905 AEAD (kind 3: the TLS 1.3 suite's cipher and
 nonce are the same), key and IV from HKDF-Expand-Label with SHA-256.
+
+--record-padding N captures the same connection under OpenSSL's block padding
+(the RecordPadding configuration command, SSL_CTX_set_block_padding): the
+temporary configuration gets a `RecordPadding = N` line, by the same child-process
+route, and the output is tests/golden/tls13_wire_padded.json (with --suite
+TLS_CHACHA20_POLY1305_SHA256: tls13_wire_chacha_padded.json), the format above
+plus "record_padding": N.  Each record's content and inner type are what is
+left of the inner plaintext without its zero padding.
 """
 import argparse
 import base64
@@ -42,6 +50,8 @@ import tls13_helper as t13  # noqa: E402
 
 PEM = os.path.join(ROOT, "tests", "golden", "server.pem")
 GOLDEN_CHACHA = os.path.join(ROOT, "tests", "golden", "tls13_wire_chacha.json")
+GOLDEN_PADDED = os.path.join(ROOT, "tests", "golden", "tls13_wire_padded.json")
+GOLDEN_CHACHA_PADDED = os.path.join(ROOT, "tests", "golden", "tls13_wire_chacha_padded.json")
 # suite -> (oracle AEAD kind, hash of the key schedule); the helper's table and ChaCha
 SUITES = dict(t13.SUITES, TLS_CHACHA20_POLY1305_SHA256=(po.CHACHA20_POLY1305, "sha256"))
 CHILD_ENV = "MAKE_TLS13_FIXTURE_CHILD"   # set in the child that runs under the suite's config
@@ -59,22 +69,30 @@ def traffic_keys(secret: bytes, suite: str):
             t13.hkdf_expand_label(secret, "iv", 12, hashname))
 
 
-def run_with_suite(suite: str, out_path: str) -> None:
-    """This tool again, in a fresh process whose OpenSSL offers `suite` alone."""
+def run_with_suite(suite: str, out_path: str, padding: int = 0) -> None:
+    """This tool again, in a fresh process whose OpenSSL offers `suite` alone
+    (None: its own choice) and pads records to blocks of `padding` bytes (0: no
+    such line)."""
     conf = tempfile.NamedTemporaryFile("w", suffix=".cnf", delete=False)
     conf.write("openssl_conf = openssl_init\n[openssl_init]\nssl_conf = ssl_sect\n"
                "[ssl_sect]\nsystem_default = system_default_sect\n"
-               "[system_default_sect]\nCiphersuites = %s\n" % suite)
+               "[system_default_sect]\n")
+    if suite:
+        conf.write("Ciphersuites = %s\n" % suite)
+    if padding:
+        conf.write("RecordPadding = %d\n" % padding)
     conf.close()
     try:
         env = dict(os.environ, OPENSSL_CONF=conf.name, **{CHILD_ENV: "1"})
-        subprocess.run([sys.executable, os.path.abspath(__file__), "--suite", suite, out_path],
+        args = (["--suite", suite] if suite else []) + \
+               (["--record-padding", str(padding)] if padding else [])
+        subprocess.run([sys.executable, os.path.abspath(__file__), *args, out_path],
                        check=True, env=env)
     finally:
         os.unlink(conf.name)
 
 
-def main(out_path: str, want_suite: str = None) -> None:
+def main(out_path: str, want_suite: str = None, padding: int = 0) -> None:
     keylog = tempfile.NamedTemporaryFile(suffix=".keylog", delete=False)
     keylog.close()
     sctx = ssl.SSLContext(ssl.PROTOCOL_TLS_SERVER)
@@ -140,6 +158,8 @@ def main(out_path: str, want_suite: str = None) -> None:
     os.unlink(keylog.name)
     orc = po.Oracle()
     fixture = {"suite": suite, "openssl": ssl.OPENSSL_VERSION, "directions": []}
+    if padding:
+        fixture["record_padding"] = padding
     for name, label in (("client", "CLIENT_TRAFFIC_SECRET_0"), ("server", "SERVER_TRAFFIC_SECRET_0")):
         kind, key, iv = traffic_keys(secrets[label], suite)
         ctx = orc.aead(kind, key)
@@ -174,13 +194,18 @@ if __name__ == "__main__":
     ap = argparse.ArgumentParser(description=__doc__.split("\n")[0])
     ap.add_argument("--suite", choices=sorted(SUITES),
                     help="negotiate this TLS 1.3 suite (default: OpenSSL's own choice)")
+    ap.add_argument("--record-padding", type=int, default=0, metavar="N",
+                    help="capture under OpenSSL's RecordPadding = N (block padding)")
     ap.add_argument("out", nargs="?")
     args = ap.parse_args()
-    if args.suite is None:
+    pad = args.record_padding
+    if args.suite is None and not pad:
         main(args.out or t13.GOLDEN)
     else:
-        out = args.out or (GOLDEN_CHACHA if "CHACHA" in args.suite else t13.GOLDEN)
+        chacha = args.suite is not None and "CHACHA" in args.suite
+        out = args.out or ((GOLDEN_CHACHA_PADDED if chacha else GOLDEN_PADDED) if pad
+                           else (GOLDEN_CHACHA if chacha else t13.GOLDEN))
         if os.environ.get(CHILD_ENV):
-            main(out, args.suite)
+            main(out, args.suite, pad)
         else:
-            run_with_suite(args.suite, out)
+            run_with_suite(args.suite, out, pad)
