@@ -81,9 +81,16 @@ enum tlsgpu_aead {
  * unexpected_message).  The output region stays as decrypted. */
 #define TLSGPU_REC_NO_CONTENT_TYPE (-6)
 
-/* Largest plaintext per record the batch kernels accept: 65534 AES blocks, so
- * GCM counters 2..nb+1 stay below 2^16 (TLS records are <= 16 KiB + 2 KiB,
- * ssl3.h:259-280).  Longer records get TLSGPU_REC_PUBLIC_INVALID. */
+/* Largest plaintext per record the AES-GCM batch kernels accept: 65534 AES
+ * blocks, so GCM counters 2..nb+1 stay below 2^16 (TLS records are <= 16 KiB +
+ * 2 KiB, ssl3.h:259-280).  A longer record of an AES-GCM session gets
+ * TLSGPU_REC_PUBLIC_INVALID and not a byte of it is written.  The limit is the
+ * AES-GCM kinds' alone: the ChaCha20-Poly1305 kernels (TLS 1.2 RFC 7905 and
+ * draft suites, and TLSGPU_CHACHA20_POLY1305_TLS13) have a 32-bit block
+ * counter, do not check it, and process a longer record like any other, up to
+ * the 24 bits of the descriptor's length (tests/test_gpu_record_limit.py pins
+ * both).  In every kind the 16-bit length in the additional data of a record
+ * above 65535 bytes is the length's low 16 bits. */
 #define TLSGPU_MAX_RECORD (65534u * 16u)
 
 /* One TLS record, 32 bytes, device-resident array.
@@ -118,9 +125,11 @@ enum tlsgpu_aead {
  *       tag verified but the inner plaintext is empty or all zero (region as
  *       decrypted).  TLSGPU_REC_BAD_MAC zero-fills all length - 16 bytes;
  *       length < 16 gives TLSGPU_REC_PUBLIC_INVALID.
- * TLSGPU_MAX_RECORD bounds the inner plaintext, and the bounds rule of
- * TLSGPU_REC_OUT_OF_BOUNDS uses these spans.  All of this holds for the three
- * TLS 1.3 kinds alike (ChaCha20-Poly1305: RFC 7905's nonce is RFC 8446's).
+ * For the AES-GCM kinds TLSGPU_MAX_RECORD bounds the inner plaintext (a seal's
+ * content is at most TLSGPU_MAX_RECORD - 1 bytes); TLSGPU_CHACHA20_POLY1305_TLS13
+ * has no such limit, as in TLS 1.2.  The bounds rule of TLSGPU_REC_OUT_OF_BOUNDS
+ * uses these spans.  All the rest holds for the three TLS 1.3 kinds alike
+ * (ChaCha20-Poly1305: RFC 7905's nonce is RFC 8446's).
  * Limits: post-handshake records only (the compatibility ChangeCipherSpec of a
  * handshake is the caller's to skip). */
 typedef struct tlsgpu_record {

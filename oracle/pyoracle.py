@@ -257,7 +257,7 @@ def tls_seal_record(impl, ctx, kind, fixed_iv, seq, rtype, pt, version=0x0303) -
 def tls_open_record(impl, ctx, kind, fixed_iv, seq, rtype, body, version=0x0303, tag_len=16):
     """(status, plaintext-or-zeros) of tls1_enc(s, 0) with `impl`."""
     gcm = kind in (AES_128_GCM, AES_256_GCM)
-    if len(body) < 8:
+    if gcm and len(body) < 8:              # the explicit nonce (eivlen) is the GCM suites' alone
         return 0, b""
     nonce = tls_nonce(kind, fixed_iv, seq, body[:8] if gcm else None)
     ct = body[8:] if gcm else body

@@ -44,6 +44,10 @@ struct BatchKnobs {
   // TLSGPU_FUSED=0 keeps the launch sequence with the device-side selection
   // instead of the fused single-kernel batches (plan_batch fused_gcm / fused_cc).
   bool fused = env_not_off("TLSGPU_FUSED");
+  // TLSGPU_CHACHA_LEGACY=1 (launch_chacha): TLS 1.2 ChaCha batches run on the
+  // per-lane kernel, which has no bounds rule and writes no initial statuses of
+  // its own, so such a batch is never fused.
+  bool cc_legacy = env_on("TLSGPU_CHACHA_LEGACY");
   // Work-balanced ranges for the fused kernel (round 5, TLSGPU_BALANCE): 0 off
   // (the default), 1 the pack variant (mixed record lengths), 2 always.  Equal
   // record counts per workgroup leave the Zipf workload's slowest CU with 16 %
@@ -328,8 +332,10 @@ static BatchPlan plan_batch(const PlanInput& in) {
   // table whose only kind is the TLS 1.3 ChaCha one: the staged ChaCha kernel
   // checks bounds and writes the statuses of the records it does not run itself
   // (chacha_kernels.hip cc_tls_wave).
+  // Not under TLSGPU_CHACHA_LEGACY, whose per-lane kernel (TLS 1.2 only) checks nothing.
   p.fused_cc = k.fused && in.bounds && !in.raw && p.cc_rfc && !aes128 && !aes256 && !p.cc_old &&
-               !have[t13 ? TLSGPU_CHACHA20_POLY1305 : TLSGPU_CHACHA20_POLY1305_TLS13];
+               !have[t13 ? TLSGPU_CHACHA20_POLY1305 : TLSGPU_CHACHA20_POLY1305_TLS13] &&
+               !(k.cc_legacy && !t13);
   const bool fused = p.fused_gcm || p.fused_cc;
   p.setup = fused ? Setup::kFused : in.bounds ? Setup::kCheckBounds : Setup::kMemset;
   p.args.fused = fused ? 1u : 0u;

@@ -20,7 +20,13 @@ tests/golden/batch_plan_trace.json, recorded by tests/golden/make_golden.py
 --batch-plan from the engine sources of commit 24b4793, BEFORE run_batch was
 split into plan_batch + execution (only this stub's trace added); the refactor
 had to reproduce every one, and so has every later change that means to keep
-the launches.
+the launches.  One change meant not to: under TLSGPU_CHACHA_LEGACY=1 a TLS 1.2
+batch of RFC 7905 ChaCha sessions only was planned as fused (no bounds pass, no
+initial statuses) although the per-lane kernel that switch selects has neither,
+so a record outside the caller's buffers was processed
+(test_gpu_tag_len.py::test_legacy_chacha_kernel_forced); plan_batch now keeps
+such a batch unfused, and that child's 20 "12:c" digests were recorded again
+from the fixed sources.  No other digest moved.
 
 The stub reports 256 CUs: the automatic split threshold is n = 512.
 Case ids: b/<generation>:<kinds>/<s|o>/<n>/h<hints>/<impl> for the batch entry

@@ -17,8 +17,10 @@ Batches hold more than 16 records per workgroup (the engine gives one
 workgroup per CU at least 16 records: above 4096 records a range is longer
 than the workgroup's 16 waves), so waves do take a second record.
 
-The helpers (RecordBatch, the oracle's TLS sessions) carry 16-byte tags only,
-so no 12-byte-tag session is included.
+The helpers used here (RecordBatch, the oracle's TLS sessions) carry 16-byte
+tags only, so no session with a shorter tag is included; test_gpu_tag_len.py
+runs tag lengths 1..16 through the same kernel variants with batches it lays
+out itself.
 """
 import os
 import sys

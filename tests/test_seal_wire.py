@@ -40,12 +40,17 @@ def engine(ta):
     e.close()
 
 
-def model_write(oracle, osess, data, seq, rtype, version, max_fragment):
-    """ssl3_write_bytes(s, type, data, len) for an AEAD suite -> wire bytes."""
+def model_write(oracle, osess, data, seq, rtype, version, max_fragment, seal=None):
+    """ssl3_write_bytes(s, type, data, len) for an AEAD suite -> wire bytes.
+    seal(seq, type, fragment) -> body replaces the oracle's TLS session, whose tag
+    has 16 bytes (test_gpu_tag_len_paths.py: tls_seal_record over an AEAD of the
+    session's tag length); the header's length is the body's, explicit nonce +
+    fragment + tag."""
+    seal = seal or (lambda s, t, piece: oracle.tls_seal(osess, s, t, piece))
     frag = max_fragment or 16384
     out, k = bytearray(), 0
     for off in range(0, len(data), frag):       # len == 0: no record at all
-        body = oracle.tls_seal(osess, seq + k, rtype, data[off:off + frag])
+        body = seal(seq + k, rtype, data[off:off + frag])
         out += bytes([rtype, version >> 8, version & 0xFF, len(body) >> 8, len(body) & 0xFF])
         out += body
         k += 1
