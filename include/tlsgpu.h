@@ -430,6 +430,80 @@ int tlsgpu_open_wire(tlsgpu_sessions *t, const tlsgpu_wire_stream *d_streams,
     int32_t *d_status, tlsgpu_wire_result *d_results, uint32_t *d_total, void *stream);
 
 /* ---------------------------------------------------------------------------
+ * Wire read path: ssl3_read_bytes (ssl/s3_pkt.c:840-1130) for many connections.
+ * tlsgpu_open_wire leaves each delivered record's plaintext where it was opened,
+ * with headers, explicit nonces, tags and (TLS 1.3) inner type bytes and padding
+ * between one record's plaintext and the next.  tlsgpu_gather_wire hands each
+ * stream's application bytes over in order as one contiguous run, and stops
+ * where a record is not application data (s3_pkt.c:938, :973-: anything else
+ * is the caller's to handle — an alert, a handshake message, change_cipher_spec).
+ *
+ * Ordered after a tlsgpu_open_wire of the same d_streams, d_recs, d_status,
+ * d_results and d_wire; asynchronous on `stream`.  It reads those five and
+ * d_reads and writes only d_app and d_read_results: d_wire is never written.
+ *
+ * Per stream i (d_reads[i] / d_read_results[i] go with d_streams[i]) it walks the
+ * records start .. delivered - 1 of the stream's wire result, in order; records
+ * at or past `delivered` (the failing one and the TLSGPU_REC_SKIPPED ones) are
+ * never looked at, and the caller reads `alert` from the wire result as before.
+ *   An application-data record (type 23 in the type bits of its descriptor's
+ *   len_type; under TLS 1.3 that is the inner type) is consumed: its `status`
+ *   bytes at out_off are appended to the stream's bytes at d_app + app_off.  An
+ *   empty one is consumed and contributes nothing (s3_pkt.c:486-488).
+ *   Any other type stops the stream with TLSGPU_READ_NOT_APP_DATA; the record
+ *   is not consumed and is described by stop_type and stop_len.
+ *   A record whose content does not fit the room left stops the stream with
+ *   TLSGPU_READ_FULL.  The room is min(app_cap, app_bytes - app_off), 0 when
+ *   app_off > app_bytes.  Records are consumed whole: unlike ssl3_read_bytes
+ *   (s3_pkt.c:952-960) there is no partial read of a record, and app_cap =
+ *   wire_len never meets the limit.
+ *   TLSGPU_READ_OUT_OF_BOUNDS: start > delivered or first + delivered >
+ *   max_records (nothing is consumed, next = start, consumed = 0), or a record
+ *   with a negative status or with [out_off, out_off + status) outside
+ *   wire_bytes (the stream stops before it; stop_type and stop_len are 0).
+ * Bytes of d_app outside [app_off, app_off + app_len) of each stream are not
+ * touched.  To go on after a stop, handle the record `next` and gather again
+ * with start = next + 1.
+ *
+ * TLSGPU_EINVAL before any GPU call: a null argument (d_recs / d_status may be
+ * null when max_records is 0), or d_app overlapping [d_wire, d_wire +
+ * wire_bytes).  n_streams == 0: TLSGPU_OK, nothing is launched.
+ * The TaLoS read hook does not run here (it is per record and may shorten one):
+ * callers that register one deliver with tlsgpu_deliver_host. */
+#define TLSGPU_READ_END 0		/* every delivered record from `start` on was consumed */
+#define TLSGPU_READ_NOT_APP_DATA 1	/* stopped before a delivered record whose type is not 23 */
+#define TLSGPU_READ_FULL 2		/* the next record's content does not fit what is left of app_cap */
+#define TLSGPU_READ_OUT_OF_BOUNDS 3	/* start > delivered, the stream's record slots leave max_records,
+					   or a record's plaintext span leaves wire_bytes: nothing copied
+					   from that record on */
+
+typedef struct tlsgpu_read_stream {	/* 16 bytes, one per wire stream, same index */
+	uint64_t app_off;	/* the stream's application bytes go to d_app + app_off */
+	uint32_t app_cap;	/* room there (SSL_read's len); wire_len always suffices */
+	uint32_t start;		/* first record of the stream to look at, index within the stream:
+				   0, or `next + 1` of an earlier gather once the caller has dealt
+				   with the record that stopped it */
+} tlsgpu_read_stream;
+
+typedef struct tlsgpu_read_result {	/* 32 bytes */
+	uint32_t app_len;	/* bytes written at app_off */
+	uint32_t records;	/* records consumed (application data; empty ones count) */
+	uint32_t next;		/* start + records: the record that stopped the stream, == delivered at END */
+	uint32_t consumed;	/* wire bytes from the stream's first byte through record next - 1 (0 if next == 0) */
+	int32_t stop;		/* TLSGPU_READ_* */
+	uint32_t stop_type;	/* NOT_APP_DATA / FULL: that record's content type (TLS 1.3: the inner type) */
+	uint32_t stop_len;	/* NOT_APP_DATA / FULL: its plaintext length; it lies at its descriptor's out_off in d_wire */
+	uint32_t reserved;
+} tlsgpu_read_result;
+
+int tlsgpu_gather_wire(tlsgpu_sessions *t,
+    const tlsgpu_wire_stream *d_streams, const tlsgpu_wire_result *d_results, uint32_t n_streams,
+    const tlsgpu_record *d_recs, const int32_t *d_status, uint32_t max_records,
+    const uint8_t *d_wire, size_t wire_bytes,
+    const tlsgpu_read_stream *d_reads, uint8_t *d_app, size_t app_bytes,
+    tlsgpu_read_result *d_read_results, void *stream);
+
+/* ---------------------------------------------------------------------------
  * Write-side framing: ssl3_write_bytes + do_ssl3_write
  * (ssl/s3_pkt.c:501-557, 560-762) for the AEAD suites, many connections at
  * once.  Each stream is one connection's SSL_write: data_len bytes of

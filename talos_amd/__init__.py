@@ -60,6 +60,13 @@ WIRE_RESULT_DTYPE = np.dtype([("first", "<u4"), ("records", "<u4"), ("delivered"
                               ("reserved", "<u4", (2,))])
 assert WIRE_STREAM_DTYPE.itemsize == 32 and WIRE_RESULT_DTYPE.itemsize == 32
 WIRE_FIRST_PACKET = 1
+# tlsgpu_read_stream / tlsgpu_read_result and the stop codes (include/tlsgpu.h, tlsgpu_gather_wire)
+READ_STREAM_DTYPE = np.dtype([("app_off", "<u8"), ("app_cap", "<u4"), ("start", "<u4")])
+READ_RESULT_DTYPE = np.dtype([("app_len", "<u4"), ("records", "<u4"), ("next", "<u4"),
+                              ("consumed", "<u4"), ("stop", "<i4"), ("stop_type", "<u4"),
+                              ("stop_len", "<u4"), ("reserved", "<u4")])
+assert READ_STREAM_DTYPE.itemsize == 16 and READ_RESULT_DTYPE.itemsize == 32
+READ_END, READ_NOT_APP_DATA, READ_FULL, READ_OUT_OF_BOUNDS = 0, 1, 2, 3
 # tlsgpu_write_stream / tlsgpu_write_result (include/tlsgpu.h)
 WRITE_STREAM_DTYPE = np.dtype([("data_off", "<u8"), ("wire_off", "<u8"), ("seq", "<u8"),
                                ("data_len", "<u4"), ("session", "<u4"), ("version", "<u2"),
@@ -149,8 +156,10 @@ def load_library(path: str = LIBPATH) -> C.CDLL:
         "tlsgpu_debug_phase_stats": (i32, [vp, C.POINTER(C.c_ulonglong), i32]),
         "tlsgpu_debug_wg_times": (i32, [vp, C.POINTER(C.c_ulonglong), C.c_uint]),
         "tlsgpu_open_wire": (i32, [vp, vp, u32, vp, u32, vp, vp, vp, vp, vp]),
+        "tlsgpu_gather_wire": (i32, [vp, vp, vp, u32, vp, vp, u32, vp, C.c_size_t, vp, vp,
+                                     C.c_size_t, vp, vp]),
         "tlsgpu_open_host": (i32, [vp, vp, u32, vp, C.c_size_t, vp, C.c_size_t, vp]),
-        "tlsgpu_seal_wire": (i32, [vp, vp, u32, vp, C.c_size_t, vp, C.c_size_t, u32, vp, vp, vp,
+        "tlsgpu_seal_wire":(i32, [vp, vp, u32, vp, C.c_size_t, vp, C.c_size_t, u32, vp, vp, vp,
                                    vp, vp]),
         "tlsgpu_seal_wire_size": (u64, [i32, u32, u32, u32]),
         "tlsgpu_seal_wire_size_v": (u64, [i32, C.c_uint16, u32, u32, u32]),
@@ -496,6 +505,18 @@ def open_wire(table: "SessionTable", d_streams: int, n_streams: int, d_wire: int
     _check(table.lib.tlsgpu_open_wire(table.handle, d_streams, n_streams, d_wire, max_records,
                                       d_recs, d_status, d_results, d_total, stream),
            "tlsgpu_open_wire")
+
+
+def gather_wire(table: "SessionTable", d_streams: int, d_results: int, n_streams: int, d_recs: int,
+                d_status: int, max_records: int, d_wire: int, wire_bytes: int, d_reads: int,
+                d_app: int, app_bytes: int, d_read_results: int, stream: int | None = None) -> None:
+    """Each stream's application bytes after an open_wire, in order and contiguous at
+    d_app + app_off, up to the first record that is not application data
+    (tlsgpu_gather_wire, ssl3_read_bytes); d_reads / d_read_results hold
+    READ_STREAM_DTYPE / READ_RESULT_DTYPE, one per stream."""
+    _check(table.lib.tlsgpu_gather_wire(table.handle, d_streams, d_results, n_streams, d_recs,
+                                        d_status, max_records, d_wire, wire_bytes, d_reads, d_app,
+                                        app_bytes, d_read_results, stream), "tlsgpu_gather_wire")
 
 
 def open_batch(table: SessionTable, d_recs: int, n: int, d_in: int, in_bytes: int, d_out: int,

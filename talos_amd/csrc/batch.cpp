@@ -384,7 +384,7 @@ static BatchPlan plan_batch(const PlanInput& in) {
 
 // Scratch of at least `bytes` for stream s (enlarging waits for the stream's
 // earlier work, which may still read the old buffer).
-static void* pre_scratch(tlsgpu_engine* e, hipStream_t s, size_t bytes) {
+void* tg::pre_scratch(tlsgpu_engine* e, hipStream_t s, size_t bytes) {
   std::lock_guard<std::mutex> g(e->pre_mu);
   PreScratch* ps = nullptr;
   for (auto& kv : e->pre)

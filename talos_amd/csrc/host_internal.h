@@ -110,6 +110,11 @@ int run_batch(tlsgpu_sessions* t, const void* d_descs, uint32_t n, const uint8_t
               const Bounds* bounds = nullptr, unsigned kinds = ~0u, unsigned hints = ~0u,
               tlsgpu_record* type_out = nullptr);
 
+// batch.cpp: stream s's grow-only scratch of at least `bytes` (null: out of
+// memory).  Work queued on s owns it until the next call for s queues more, so
+// a pass that uses it must finish reading it in the launches it queues.
+void* pre_scratch(tlsgpu_engine* e, hipStream_t s, size_t bytes);
+
 inline uint64_t mono_ns() {
   return (uint64_t)std::chrono::duration_cast<std::chrono::nanoseconds>(
              std::chrono::steady_clock::now().time_since_epoch())

@@ -1,7 +1,7 @@
 // host_paths.cpp — the batch ABI's paths around run_batch for data that starts
 // or ends on the host or on the wire: the host-resident pipeline
 // (tlsgpu_open_host / tlsgpu_seal_host), session owners and host delivery with
-// the TaLoS plaintext hooks, wire open and seal, and the synthetic fills.
+// the TaLoS plaintext hooks, wire open, gather and seal, and the synthetic fills.
 #include "host_internal.h"
 
 using namespace tg;
@@ -350,6 +350,65 @@ extern "C" int tlsgpu_open_wire(tlsgpu_sessions* t, const tlsgpu_wire_stream* d_
   }
   if (launch_wire_finish(n_streams, d_results, d_status, s))
     return fail(TLSGPU_EHIP, "wire finish launch: %s", hipGetErrorString(hipGetLastError()));
+  return TLSGPU_OK;
+}
+
+// The copy kernel's piece size from what the host knows of the batch, the wire
+// bytes per record slot: long records are split over 8 waves each, short ones
+// get one wave (kGatherSplitBytes).  TLSGPU_GATHER_PIECE=2048 /
+// 4096 / 16384 forces one (experiments only).
+static const uint32_t g_gather_piece = (uint32_t)env_uint("TLSGPU_GATHER_PIECE", 0, 10);
+static uint32_t gather_piece(size_t wire_bytes, uint32_t max_records) {
+  if (g_gather_piece) return g_gather_piece;
+  return max_records && wire_bytes / max_records > kGatherSplitBytes ? kGatherPiece : kGatherWhole;
+}
+
+// The two launchers are weak references in this unit: the kernels' object
+// defines them in libtlsgpu.so, but a link of the host objects alone against a
+// launcher list written before this call existed (the CPU tests' recording HIP
+// stub) must still resolve.  There the call fails loudly, before any HIP call.
+namespace tg {
+__attribute__((weak)) int launch_wire_gather_plan(
+    const tlsgpu_wire_stream* streams, const tlsgpu_wire_result* results, uint32_t n_streams,
+    const tlsgpu_record* recs, const int32_t* status, uint32_t max_records, uint64_t wire_bytes,
+    const tlsgpu_read_stream* reads, uint64_t app_bytes, uint64_t* dst, tlsgpu_read_result* out,
+    hipStream_t s);
+__attribute__((weak)) int launch_wire_gather_copy(
+    const tlsgpu_record* recs, const int32_t* status, uint32_t max_records, const uint8_t* wire,
+    uint64_t wire_bytes, const uint64_t* dst, uint8_t* app, uint64_t app_bytes, uint32_t piece,
+    hipStream_t s);
+}  // namespace tg
+
+extern "C" int tlsgpu_gather_wire(tlsgpu_sessions* t, const tlsgpu_wire_stream* d_streams,
+                                  const tlsgpu_wire_result* d_results, uint32_t n_streams,
+                                  const tlsgpu_record* d_recs, const int32_t* d_status,
+                                  uint32_t max_records, const uint8_t* d_wire, size_t wire_bytes,
+                                  const tlsgpu_read_stream* d_reads, uint8_t* d_app,
+                                  size_t app_bytes, tlsgpu_read_result* d_read_results,
+                                  void* stream) {
+  if (!t || (n_streams && (!d_streams || !d_results || !d_wire || !d_reads || !d_app ||
+                           !d_read_results)) ||
+      (max_records && (!d_recs || !d_status)))
+    return fail(TLSGPU_EINVAL, "bad arguments");
+  // the copy reads d_wire while it writes d_app: the two may not share a byte
+  const uintptr_t w0 = (uintptr_t)d_wire, a0 = (uintptr_t)d_app;
+  if (d_wire && d_app && a0 < w0 + wire_bytes && w0 < a0 + app_bytes)
+    return fail(TLSGPU_EINVAL, "d_app overlaps d_wire");
+  if (n_streams == 0) return TLSGPU_OK;
+  if (!launch_wire_gather_plan || !launch_wire_gather_copy)
+    return fail(TLSGPU_EHIP, "the gather kernels are not linked into this library");
+  HIPCHK(hipSetDevice(t->eng->device));
+  hipStream_t s = stream ? (hipStream_t)stream : t->eng->stream;
+  // one destination offset per record slot, "no copy" until the plan says otherwise
+  uint64_t* dst = (uint64_t*)pre_scratch(t->eng, s, sizeof(uint64_t) * (size_t)max_records);
+  if (!dst) return fail(TLSGPU_ENOMEM, "gather scratch (%u records)", max_records);
+  if (max_records) HIPCHK(hipMemsetAsync(dst, 0xFF, sizeof(uint64_t) * (size_t)max_records, s));
+  if (launch_wire_gather_plan(d_streams, d_results, n_streams, d_recs, d_status, max_records,
+                              wire_bytes, d_reads, app_bytes, dst, d_read_results, s))
+    return fail(TLSGPU_EHIP, "wire gather plan launch: %s", hipGetErrorString(hipGetLastError()));
+  if (launch_wire_gather_copy(d_recs, d_status, max_records, d_wire, wire_bytes, dst, d_app,
+                              app_bytes, gather_piece(wire_bytes, max_records), s))
+    return fail(TLSGPU_EHIP, "wire gather copy launch: %s", hipGetErrorString(hipGetLastError()));
   return TLSGPU_OK;
 }
 

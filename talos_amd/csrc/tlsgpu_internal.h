@@ -419,6 +419,27 @@ int launch_wire_seal_frame(const tlsgpu_write_stream* streams, uint32_t n_stream
                            tlsgpu_write_result* results, uint32_t* total, hipStream_t s);
 int launch_wire_finish(uint32_t n_streams, tlsgpu_wire_result* results, int32_t* status,
                        hipStream_t s);
+// tlsgpu_gather_wire (wire_kernels.hip): the plan writes, per record slot it
+// takes, the record's absolute destination offset into dst[max_records], which
+// the caller has preset to kNoGather (bytes of 0xFF); the copy moves the slots
+// that have one.  piece: bytes of a record per wave, 16384 / piece waves per
+// record slot: kGatherPiece where the wire buffer holds more than
+// kGatherSplitBytes per record slot (long records: 8 waves each), else
+// kGatherWhole (one wave per slot; the waves of pieces a short record does not
+// have cost more than splitting gains: DESIGN.md §4.6b has the measurement the
+// threshold comes from).  4096 is compiled too (TLSGPU_GATHER_PIECE forces one
+// of the three, experiments only).
+constexpr uint64_t kNoGather = ~0ull;
+constexpr uint32_t kGatherPiece = 2048, kGatherWhole = 16384;
+constexpr uint64_t kGatherSplitBytes = 9216;
+int launch_wire_gather_plan(const tlsgpu_wire_stream* streams, const tlsgpu_wire_result* results,
+                            uint32_t n_streams, const tlsgpu_record* recs, const int32_t* status,
+                            uint32_t max_records, uint64_t wire_bytes,
+                            const tlsgpu_read_stream* reads, uint64_t app_bytes, uint64_t* dst,
+                            tlsgpu_read_result* out, hipStream_t s);
+int launch_wire_gather_copy(const tlsgpu_record* recs, const int32_t* status, uint32_t max_records,
+                            const uint8_t* wire, uint64_t wire_bytes, const uint64_t* dst,
+                            uint8_t* app, uint64_t app_bytes, uint32_t piece, hipStream_t s);
 int launch_fill_synthetic(uint8_t* d_out, uint64_t stride, uint32_t span_len,
                           uint32_t n, uint64_t seed, uint64_t index0, hipStream_t s);
 int launch_upload_session(const void* img, DevSession* sess, DevGcmTables* tab,

@@ -11,7 +11,12 @@
 //                       reference's alerts in record order (:385-390 decryption
 //                       failed, :450-462 bad_record_mac, :465-469 record
 //                       overflow) and marks the records after the first failure
-//                       as not delivered.
+//                       as not delivered;
+//   wire_gather_plan_kernel  one wave per stream, after an open: which
+//                       delivered records ssl3_read_bytes (s3_pkt.c:840-1130)
+//                       would hand the application and where each one's bytes
+//                       land in the stream's contiguous region (tlsgpu_gather_wire);
+//   wire_gather_copy_kernel  one wave per piece of a record: the copy itself.
 // Header walks are a dependent chain of small reads per stream: the parallelism
 // is across streams (connections), as a server's batch has it, and each round
 // trip covers many headers (wire_walk).
@@ -449,6 +454,181 @@ __global__ __launch_bounds__(256) void wire_seal_frame_kernel(
   results[i] = res;
 }
 
+// ---------------------------------------------------------------------------
+// tlsgpu_gather_wire: ssl3_read_bytes (s3_pkt.c:840-1130) for many connections,
+// after tlsgpu_open_wire has left each delivered record's plaintext at its
+// descriptor's out_off and its content type in the descriptor's type bits.
+
+// inclusive wave scan of a 64-bit value (wave_reserve's pattern); all 64 lanes active
+__device__ __forceinline__ uint64_t wave_scan64(uint64_t v, uint32_t lane) {
+#pragma unroll
+  for (int d = 1; d < 64; d <<= 1) {
+    const uint32_t lo = __shfl_up((uint32_t)v, d), hi = __shfl_up((uint32_t)(v >> 32), d);
+    if (lane >= (uint32_t)d) v += ((uint64_t)hi << 32) | lo;
+  }
+  return v;
+}
+
+// One wave per stream (four per workgroup, as wire_finish_kernel), 64 records
+// per step.  The only place the rule is written: a stream's records start ..
+// delivered - 1 are taken in order while each is application data (type 23,
+// s3_pkt.c:938), its plaintext span lies inside the wire buffer and its
+// content still fits the room left; a taken record of length > 0 gets its
+// absolute destination offset in dst[slot] (the copy kernel's work list, preset
+// to kNoGather), an empty one is taken and copies nothing (:486-488).  Records
+// are taken whole.
+__global__ __launch_bounds__(256) void wire_gather_plan_kernel(
+    const tlsgpu_wire_stream* __restrict__ streams, const tlsgpu_wire_result* __restrict__ results,
+    uint32_t n_streams, const tlsgpu_record* __restrict__ recs, const int32_t* __restrict__ status,
+    uint32_t max_records, uint64_t wire_bytes, const tlsgpu_read_stream* __restrict__ reads,
+    uint64_t app_bytes, uint64_t* __restrict__ dst, tlsgpu_read_result* __restrict__ out) {
+  const uint32_t lane = threadIdx.x & 63;
+  const uint32_t s = blockIdx.x * 4 + uni(threadIdx.x >> 6);
+  if (s >= n_streams) return;
+  const tlsgpu_wire_result wr = results[s];
+  const tlsgpu_read_stream rd = reads[s];
+  tlsgpu_read_result r = {};
+  r.next = rd.start;
+  if (rd.start > wr.delivered || (uint64_t)wr.first + wr.delivered > max_records) {
+    r.stop = TLSGPU_READ_OUT_OF_BOUNDS;
+    if (lane == 0) out[s] = r;
+    return;
+  }
+  uint32_t room = rd.app_cap;  // min(app_cap, app_bytes - app_off), 0 past the buffer's end
+  if (rd.app_off > app_bytes) room = 0;
+  else if (app_bytes - rd.app_off < room) room = (uint32_t)(app_bytes - rd.app_off);
+  uint64_t total = 0;  // application bytes of the records taken so far (<= room)
+  for (uint64_t i0 = rd.start; i0 < wr.delivered; i0 += 64) {
+    const uint32_t nin = (uint32_t)min((uint64_t)64, wr.delivered - i0);  // records of this step
+    const bool in = lane < nin;
+    const size_t slot = (size_t)wr.first + i0 + lane;
+    uint32_t lt = 0;
+    int32_t st = 0;
+    uint64_t off = 0;
+    if (in) {
+      lt = recs[slot].len_type;
+      off = recs[slot].out_off;
+      st = status[slot];
+    }
+    const uint32_t len = (uint32_t)st;
+    const bool span_ok = st >= 0 && off <= wire_bytes && len <= wire_bytes - off;
+    const bool app = (lt >> 24) == kAppData;
+    const uint64_t incl = wave_scan64(in && span_ok && app ? len : 0u, lane);
+    const uint64_t before = total + incl - (in && span_ok && app ? len : 0u);
+    const int32_t code = !in             ? TLSGPU_READ_END
+                         : !span_ok      ? TLSGPU_READ_OUT_OF_BOUNDS
+                         : !app          ? TLSGPU_READ_NOT_APP_DATA
+                         : before + len > room ? TLSGPU_READ_FULL
+                                         : TLSGPU_READ_END;
+    const uint64_t stops = __ballot(code != TLSGPU_READ_END);
+    const uint32_t take = stops ? min((uint32_t)__builtin_ctzll(stops), nin) : nin;
+    if (lane < take && len) dst[slot] = rd.app_off + before;
+    r.records += take;
+    if (take) {
+      const uint32_t lo = __shfl((uint32_t)incl, (int)take - 1);
+      const uint32_t hi = __shfl((uint32_t)(incl >> 32), (int)take - 1);
+      total += ((uint64_t)hi << 32) | lo;
+    }
+    if (stops) {
+      const int fl = __builtin_ctzll(stops);
+      r.stop = __shfl(code, fl);
+      if (r.stop != TLSGPU_READ_OUT_OF_BOUNDS) {
+        r.stop_type = __shfl(lt >> 24, fl);
+        r.stop_len = __shfl(len, fl);
+      }
+      break;
+    }
+  }
+  if (lane == 0) {
+    r.app_len = (uint32_t)total;
+    r.next = rd.start + r.records;
+    if (r.next) {  // the wire bytes through record next - 1: the end of its fragment
+      const tlsgpu_record last = recs[(size_t)wr.first + r.next - 1];
+      r.consumed = (uint32_t)(last.in_off + (last.len_type & 0xFFFFFFu) - streams[s].wire_off);
+    }
+    out[s] = r;
+  }
+}
+
+// The first nb (0..16) bytes of block o at any byte address p: the widest
+// naturally aligned stores that stay inside [p, p + nb) — a byte and a short up
+// to the first dword boundary, whole dwords, a short and a byte after the last.
+// Never a read-modify-write: the bytes around belong to other waves.
+__device__ __forceinline__ void store16_upto(uint8_t* p, uint32_t nb, const uint32_t o[4]) {
+  // 4 / 2 / 1 bytes of the block from byte i on (i <= 15)
+  auto at = [&](uint32_t i) {
+    const uint32_t w = i >> 2;
+    const uint32_t lo = w == 0 ? o[0] : w == 1 ? o[1] : w == 2 ? o[2] : o[3];
+    const uint32_t hi = w == 0 ? o[1] : w == 1 ? o[2] : w == 2 ? o[3] : 0u;
+    return __builtin_amdgcn_alignbyte(hi, lo, i & 3u);
+  };
+  const uint32_t a = (uint32_t)(uintptr_t)p;
+  uint32_t i = 0;
+  if ((a & 1u) && i < nb) {
+    gst<uint8_t>(p)[0] = (uint8_t)at(0);
+    i = 1;
+  }
+  if (((a + i) & 2u) && i + 2 <= nb) {
+    gst<uint16_t>(p + i)[0] = (uint16_t)at(i);
+    i += 2;
+  }
+  for (; i + 4 <= nb; i += 4) gst<uint32_t>(p + i)[0] = at(i);
+  if (i + 2 <= nb) {
+    gst<uint16_t>(p + i)[0] = (uint16_t)at(i);
+    i += 2;
+  }
+  if (i < nb) gst<uint8_t>(p + i)[0] = (uint8_t)at(i);
+}
+
+// The copy: one wave per piece of PIECE bytes of one record slot, 16384 / PIECE
+// waves per slot (so a 16 KiB record is spread over that many waves; a record
+// of the engine's wider range takes its further pieces in the same waves'
+// loop), four waves per workgroup.  A slot without a destination costs its
+// wave one 8-byte load.  Within a piece: the bytes up to
+// the destination's first 16-B boundary (lane 0) and after its last (lane 1)
+// go out byte-exact (load16_upto + store16_upto), every block between as one
+// aligned 16-B store per lane of a source block at any byte offset
+// (load16_any: only dwords that hold a byte of the record are read).
+template <uint32_t PIECE>
+__global__ __launch_bounds__(256) void wire_gather_copy_kernel(
+    const tlsgpu_record* __restrict__ recs, const int32_t* __restrict__ status,
+    uint32_t max_records, const uint8_t* __restrict__ wire, uint64_t wire_bytes,
+    const uint64_t* __restrict__ dst, uint8_t* __restrict__ app, uint64_t app_bytes) {
+  constexpr uint32_t kPieces = kMaxPlain / PIECE;  // waves per record slot
+  const uint32_t lane = threadIdx.x & 63;
+  const uint64_t g = (uint64_t)blockIdx.x * 4 + uni(threadIdx.x >> 6);
+  const uint64_t slot = g / kPieces;
+  if (slot >= max_records) return;
+  const uint64_t d = dst[slot];
+  if (d == kNoGather) return;
+  const uint32_t len = (uint32_t)status[slot];
+  uint32_t pos = (uint32_t)(g % kPieces) * PIECE;
+  if (pos >= len) return;
+  const uint64_t src = recs[slot].out_off;
+  // (the plan checked both spans; a slot two streams claim is still copied inside them)
+  if (src > wire_bytes || len > wire_bytes - src || d > app_bytes || len > app_bytes - d) return;
+  for (; pos < len; pos += kMaxPlain) {
+    const uint8_t* sp = wire + src + pos;
+    uint8_t* dp = app + d + pos;
+    const uint32_t n = min(PIECE, len - pos);
+    const uint32_t head = min((uint32_t)(-(uintptr_t)dp & 15u), n);
+    const uint32_t blocks = (n - head) >> 4, tail = (n - head) & 15u;
+    if (lane < 2) {  // lane 0: the head, lane 1: the tail
+      const uint32_t o = lane ? head + 16 * blocks : 0u, nb = lane ? tail : head;
+      if (nb) {
+        uint32_t v[4];
+        load16_upto(sp + o, nb, v);
+        store16_upto(dp + o, nb, v);
+      }
+    }
+    for (uint32_t b = lane; b < blocks; b += 64) {
+      uint32_t v[4];
+      load16_any(sp + head + 16 * b, v);
+      gstore16(dp + head + 16 * b, make_uint4(v[0], v[1], v[2], v[3]));
+    }
+  }
+}
+
 int launch_wire_seal_frame(const tlsgpu_write_stream* streams, uint32_t n_streams,
                            const DevSession* sessions, uint32_t n_sessions, uint8_t* wire,
                            uint64_t wire_bytes, uint32_t max_records, tlsgpu_record* recs,
@@ -477,6 +657,41 @@ int launch_wire_finish(uint32_t n_streams, tlsgpu_wire_result* results, int32_t*
   hipLaunchKernelGGL(wire_finish_kernel, dim3((n_streams + 3) / 4), dim3(256), 0, s, n_streams,
                      results, status);
   return hipGetLastError() == hipSuccess ? 0 : -1;
+}
+
+int launch_wire_gather_plan(const tlsgpu_wire_stream* streams, const tlsgpu_wire_result* results,
+                            uint32_t n_streams, const tlsgpu_record* recs, const int32_t* status,
+                            uint32_t max_records, uint64_t wire_bytes,
+                            const tlsgpu_read_stream* reads, uint64_t app_bytes, uint64_t* dst,
+                            tlsgpu_read_result* out, hipStream_t s) {
+  if (n_streams == 0) return 0;
+  hipLaunchKernelGGL(wire_gather_plan_kernel, dim3((n_streams + 3) / 4), dim3(256), 0, s, streams,
+                     results, n_streams, recs, status, max_records, wire_bytes, reads, app_bytes,
+                     dst, out);
+  return hipGetLastError() == hipSuccess ? 0 : -1;
+}
+
+template <uint32_t PIECE>
+static int gather_copy(const tlsgpu_record* recs, const int32_t* status, uint32_t max_records,
+                       const uint8_t* wire, uint64_t wire_bytes, const uint64_t* dst, uint8_t* app,
+                       uint64_t app_bytes, hipStream_t s) {
+  const uint64_t waves = (uint64_t)max_records * (kMaxPlain / PIECE);
+  const uint64_t groups = (waves + 3) / 4;
+  if (groups > 0x7FFFFFFFull) return -1;
+  hipLaunchKernelGGL(wire_gather_copy_kernel<PIECE>, dim3((uint32_t)groups), dim3(256), 0, s, recs,
+                     status, max_records, wire, wire_bytes, dst, app, app_bytes);
+  return hipGetLastError() == hipSuccess ? 0 : -1;
+}
+
+int launch_wire_gather_copy(const tlsgpu_record* recs, const int32_t* status, uint32_t max_records,
+                            const uint8_t* wire, uint64_t wire_bytes, const uint64_t* dst,
+                            uint8_t* app, uint64_t app_bytes, uint32_t piece, hipStream_t s) {
+  if (max_records == 0) return 0;
+  switch (piece) {
+    case kGatherPiece: return gather_copy<kGatherPiece>(recs, status, max_records, wire, wire_bytes, dst, app, app_bytes, s);
+    case 4096: return gather_copy<4096>(recs, status, max_records, wire, wire_bytes, dst, app, app_bytes, s);
+    default: return gather_copy<kGatherWhole>(recs, status, max_records, wire, wire_bytes, dst, app, app_bytes, s);
+  }
 }
 
 }  // namespace tg
