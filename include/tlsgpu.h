@@ -422,8 +422,71 @@ typedef struct tlsgpu_wire_result {
 	uint32_t consumed;	/* bytes of the framed records (header + fragment) */
 	int32_t alert;		/* 0, a fatal TLS AlertDescription, or -1 (error, no alert) */
 	uint32_t alert_record;	/* index within the stream of the record that failed */
-	uint32_t reserved[2];
+	uint32_t key_update;	/* TLSGPU_WIRE_KU_* (tlsgpu_sessions_wire_key_update); else 0 */
+	uint32_t reserved;
 } tlsgpu_wire_result;
+
+/* ---------------------------------------------------------------------------
+ * KeyUpdate on the wire read path (RFC 8446 4.6.3, 7.2).  Every record behind a
+ * KeyUpdate is protected under the next traffic keys with the sequence number
+ * back at 0, so a read-ahead that holds one cannot be opened under one session:
+ * the records behind it would fail their tags and be zero-filled in d_wire.
+ *
+ * tlsgpu_sessions_wire_key_update(t, 1) makes tlsgpu_open_wire cut a stream at
+ * a KeyUpdate BEFORE anything behind it is opened.  A per-table switch, off by
+ * default; it is not a hint, results depend on it.  It acts on tlsgpu_open_wire
+ * only, and there only on streams whose session is a TLS 1.3 session; on a
+ * TLS 1.2 table it is accepted and changes nothing.  A null table is
+ * TLSGPU_EINVAL.  With the switch off tlsgpu_open_wire is what it was, and
+ * key_update is always TLSGPU_WIRE_KU_NONE (as it is for TLS 1.2 streams and
+ * streams of unknown sessions with the switch on).
+ *
+ * The rule.  Between framing and the open, the engine decrypts the first
+ * min(16, inner length) bytes of every framed record (one cipher block, no
+ * authentication) and takes the first record of the stream whose
+ * TLSInnerPlaintext begins 18 00 00 01 rr 16 (rr <= 1) with only zeros up to
+ * byte 15 as the candidate: a KeyUpdate handshake message alone in its record.
+ * The stream is cut after the candidate:
+ *   records = the candidate's index + 1, consumed ends with its last byte;
+ *   a header-level alert that framing found behind the cut is dropped (alert =
+ *   0, alert_record = records; the next call finds it again);
+ *   the descriptor slots framing had reserved behind the cut are reset to all
+ *   ones like unused slots (d_total still counts them, their statuses are what
+ *   the open leaves for unused slots);
+ *   not one byte of d_wire from wire_off + consumed on is read by the open or
+ *   written by anyone.
+ * The peek is unauthenticated, so it decides only where the batch is cut, never
+ * what the caller is told: a look-alike or a forgery costs the stream a shorter
+ * batch and nothing else.  key_update is set after the normal open, from the
+ * verified record:
+ *   TLSGPU_WIRE_KU_UPDATE            record records - 1 was delivered, is of inner
+ *                                    type 22 and its content is exactly 18 00 00 01 00;
+ *   TLSGPU_WIRE_KU_UPDATE_REQUESTED  the same with 18 00 00 01 01: the caller also
+ *                                    owes the peer a KeyUpdate of its own;
+ *   TLSGPU_WIRE_KU_HELD              the stream was cut after record records - 1, but
+ *                                    that record is no KeyUpdate: it failed its tag
+ *                                    (`alert` says so as usual), or it verified with
+ *                                    another type or other content.  Go on from
+ *                                    `consumed` under the same keys with seq +
+ *                                    records, unless `alert` ended the stream.
+ * After TLSGPU_WIRE_KU_UPDATE*: derive application_traffic_secret_N+1 =
+ * HKDF-Expand-Label(secret_N, "traffic upd", "", Hash.length) and its key and IV
+ * on the host, install them into the stream's read session slot
+ * (tlsgpu_sessions_install, between batches as always), and make the next call
+ * at wire_off + consumed with seq = 0.  tlsgpu_gather_wire stops at the
+ * KeyUpdate record with TLSGPU_READ_NOT_APP_DATA, stop_type 22, stop_len 5.
+ * Limits: a KeyUpdate that follows another handshake message inside one record,
+ * or one split over two records, is not seen by the peek; such a stream behaves
+ * as with the switch off.  There is no second session per stream: the bytes
+ * behind the cut are never opened in the same call (under pre-installed next
+ * keys a look-alike would destroy the connection).  The engine derives no
+ * traffic secrets and sends no KeyUpdate: the write side is a tlsgpu_seal_wire
+ * stream of type 22 with the 5-byte message, then a reinstall of the write slot. */
+#define TLSGPU_WIRE_KU_NONE 0
+#define TLSGPU_WIRE_KU_UPDATE 1
+#define TLSGPU_WIRE_KU_UPDATE_REQUESTED 2
+#define TLSGPU_WIRE_KU_HELD 3
+int tlsgpu_sessions_wire_key_update(tlsgpu_sessions *t, int on);
 
 int tlsgpu_open_wire(tlsgpu_sessions *t, const tlsgpu_wire_stream *d_streams,
     uint32_t n_streams, uint8_t *d_wire, uint32_t max_records, tlsgpu_record *d_recs,

@@ -60,6 +60,14 @@ WIRE_RESULT_DTYPE = np.dtype([("first", "<u4"), ("records", "<u4"), ("delivered"
                               ("reserved", "<u4", (2,))])
 assert WIRE_STREAM_DTYPE.itemsize == 32 and WIRE_RESULT_DTYPE.itemsize == 32
 WIRE_FIRST_PACKET = 1
+# tlsgpu_wire_result with its key_update field named (the same 32 bytes: view a
+# WIRE_RESULT_DTYPE array as this one; WIRE_RESULT_DTYPE keeps its seven fields
+# for callers that fill it from tuples) and the TLSGPU_WIRE_KU_* values
+WIRE_RESULT_KU_DTYPE = np.dtype([("first", "<u4"), ("records", "<u4"), ("delivered", "<u4"),
+                                 ("consumed", "<u4"), ("alert", "<i4"), ("alert_record", "<u4"),
+                                 ("key_update", "<u4"), ("reserved", "<u4")])
+assert WIRE_RESULT_KU_DTYPE.itemsize == 32 and WIRE_RESULT_KU_DTYPE.fields["key_update"][1] == 24
+WIRE_KU_NONE, WIRE_KU_UPDATE, WIRE_KU_UPDATE_REQUESTED, WIRE_KU_HELD = 0, 1, 2, 3
 # tlsgpu_read_stream / tlsgpu_read_result and the stop codes (include/tlsgpu.h, tlsgpu_gather_wire)
 READ_STREAM_DTYPE = np.dtype([("app_off", "<u8"), ("app_cap", "<u4"), ("start", "<u4")])
 READ_RESULT_DTYPE = np.dtype([("app_len", "<u4"), ("records", "<u4"), ("next", "<u4"),
@@ -145,6 +153,7 @@ def load_library(path: str = LIBPATH) -> C.CDLL:
         "tlsgpu_sessions_destroy": (None, [vp]),
         "tlsgpu_sessions_install": (i32, [vp, u32, u32, vp]),
         "tlsgpu_sessions_hint": (i32, [vp, u32]),
+        "tlsgpu_sessions_wire_key_update": (i32, [vp, i32]),
         "tlsgpu_open_batch": (i32, [vp, vp, u32, vp, C.c_size_t, vp, C.c_size_t, vp, vp]),
         "tlsgpu_seal_batch": (i32, [vp, vp, u32, vp, C.c_size_t, vp, C.c_size_t, vp, vp]),
         "tlsgpu_fill_synthetic": (i32, [vp, vp, u64, u32, u32, u64, u64, vp]),
@@ -505,6 +514,15 @@ def open_wire(table: "SessionTable", d_streams: int, n_streams: int, d_wire: int
     _check(table.lib.tlsgpu_open_wire(table.handle, d_streams, n_streams, d_wire, max_records,
                                       d_recs, d_status, d_results, d_total, stream),
            "tlsgpu_open_wire")
+
+
+def sessions_wire_key_update(table: "SessionTable", on: bool) -> None:
+    """The table's KeyUpdate switch (tlsgpu_sessions_wire_key_update), off by
+    default: open_wire then cuts a TLS 1.3 stream after a KeyUpdate record, with
+    the bytes behind it untouched, and says so in the wire result's key_update
+    (WIRE_KU_*; view the results as WIRE_RESULT_KU_DTYPE).  Not a hint."""
+    _check(table.lib.tlsgpu_sessions_wire_key_update(table.handle, int(bool(on))),
+           "tlsgpu_sessions_wire_key_update")
 
 
 def gather_wire(table: "SessionTable", d_streams: int, d_results: int, n_streams: int, d_recs: int,

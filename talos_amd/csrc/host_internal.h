@@ -71,6 +71,8 @@ struct tlsgpu_sessions {
                                // the first install, one generation per table
   bool have[tg::kKinds];       // any session of kind k installed (enum tlsgpu_aead)
   std::atomic<unsigned> hints{0};  // TLSGPU_HINT_* (tlsgpu_sessions_hint)
+  std::atomic<bool> wire_key_update{false};  // tlsgpu_sessions_wire_key_update: tlsgpu_open_wire
+                                             // cuts TLS 1.3 streams at a KeyUpdate (not a hint)
   // EVP contexts: per-slot event of the slot's last install or scrub, so init
   // and cleanup need not wait on the device (created on a slot's first use)
   std::vector<hipEvent_t> slot_ev;

@@ -323,6 +323,27 @@ extern "C" int tlsgpu_hook_write_streams(tlsgpu_sessions* t, const tlsgpu_write_
   return TLSGPU_OK;
 }
 
+// The KeyUpdate cut of tlsgpu_open_wire (include/tlsgpu.h): a
+// per-table switch, and two launchers that are weak references here for the
+// reason the gather's are (below): a library linked without wire_peek.hip's
+// kernels fails loudly, and only when the switch is on.
+namespace tg {
+__attribute__((weak)) int launch_wire_peek13(
+    const tlsgpu_wire_stream* streams, uint32_t n_streams, const uint8_t* wire,
+    const DevSession* sessions, uint32_t n_sessions, uint32_t max_records, tlsgpu_record* recs,
+    tlsgpu_wire_result* results, hipStream_t s);
+__attribute__((weak)) int launch_wire_ku_confirm(
+    const tlsgpu_wire_stream* streams, uint32_t n_streams, const uint8_t* wire,
+    uint32_t max_records, const tlsgpu_record* recs, const int32_t* status,
+    tlsgpu_wire_result* results, hipStream_t s);
+}  // namespace tg
+
+extern "C" int tlsgpu_sessions_wire_key_update(tlsgpu_sessions* t, int on) {
+  if (!t) return fail(TLSGPU_EINVAL, "bad arguments");
+  t->wire_key_update.store(on != 0, std::memory_order_relaxed);
+  return TLSGPU_OK;
+}
+
 extern "C" int tlsgpu_open_wire(tlsgpu_sessions* t, const tlsgpu_wire_stream* d_streams,
                                 uint32_t n_streams, uint8_t* d_wire, uint32_t max_records,
                                 tlsgpu_record* d_recs, int32_t* d_status,
@@ -330,6 +351,11 @@ extern "C" int tlsgpu_open_wire(tlsgpu_sessions* t, const tlsgpu_wire_stream* d_
   if (!t || !d_total || (n_streams && (!d_streams || !d_wire || !d_results)) ||
       (max_records && (!d_recs || !d_status)))
     return fail(TLSGPU_EINVAL, "bad arguments");
+  const bool ku = t->wire_key_update.load(std::memory_order_relaxed);
+  if (ku && (!launch_wire_peek13 || !launch_wire_ku_confirm))
+    return fail(TLSGPU_EHIP, "the KeyUpdate kernels are not linked into this library");
+  // the cut: TLS 1.3 streams only, and only where there are descriptors to cut
+  const bool cut = ku && t->generation == 13 && max_records;
   HIPCHK(hipSetDevice(t->eng->device));
   hipStream_t s = stream ? (hipStream_t)stream : t->eng->stream;
   HIPCHK(hipMemsetAsync(d_total, 0, sizeof(uint32_t), s));
@@ -341,6 +367,10 @@ extern "C" int tlsgpu_open_wire(tlsgpu_sessions* t, const tlsgpu_wire_stream* d_
   if (launch_wire_frame(d_streams, n_streams, d_wire, t->d_sess, t->capacity, max_records, d_recs,
                         d_results, d_total, s))
     return fail(TLSGPU_EHIP, "wire frame launch: %s", hipGetErrorString(hipGetLastError()));
+  // before anything is opened: what lies behind a KeyUpdate stays ciphertext
+  if (cut && launch_wire_peek13(d_streams, n_streams, d_wire, t->d_sess, t->capacity, max_records,
+                                d_recs, d_results, s))
+    return fail(TLSGPU_EHIP, "wire peek launch: %s", hipGetErrorString(hipGetLastError()));
   if (max_records) {
     // TLS 1.3: the open's unpad pass leaves every record's inner content type
     // in its descriptor's type bits, as a TLS 1.2 record's header type is
@@ -350,6 +380,11 @@ extern "C" int tlsgpu_open_wire(tlsgpu_sessions* t, const tlsgpu_wire_stream* d_
   }
   if (launch_wire_finish(n_streams, d_results, d_status, s))
     return fail(TLSGPU_EHIP, "wire finish launch: %s", hipGetErrorString(hipGetLastError()));
+  // the verdict, from the verified record alone
+  if (cut && launch_wire_ku_confirm(d_streams, n_streams, d_wire, max_records, d_recs, d_status,
+                                    d_results, s))
+    return fail(TLSGPU_EHIP, "wire KeyUpdate confirm launch: %s",
+                hipGetErrorString(hipGetLastError()));
   return TLSGPU_OK;
 }
 

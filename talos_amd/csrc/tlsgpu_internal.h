@@ -440,6 +440,18 @@ int launch_wire_gather_plan(const tlsgpu_wire_stream* streams, const tlsgpu_wire
 int launch_wire_gather_copy(const tlsgpu_record* recs, const int32_t* status, uint32_t max_records,
                             const uint8_t* wire, uint64_t wire_bytes, const uint64_t* dst,
                             uint8_t* app, uint64_t app_bytes, uint32_t piece, hipStream_t s);
+// tlsgpu_open_wire with the table's KeyUpdate switch on (wire_peek.hip).  The
+// peek runs between launch_wire_frame and the open: it cuts every TLS 1.3 stream
+// after its first record whose first plaintext block looks like a KeyUpdate
+// (descriptors behind it back to all ones, the result rewritten, key_update =
+// TLSGPU_WIRE_KU_HELD).  The confirmation runs after launch_wire_finish and
+// turns HELD into TLSGPU_WIRE_KU_UPDATE / _REQUESTED from the verified record.
+int launch_wire_peek13(const tlsgpu_wire_stream* streams, uint32_t n_streams, const uint8_t* wire,
+                       const DevSession* sessions, uint32_t n_sessions, uint32_t max_records,
+                       tlsgpu_record* recs, tlsgpu_wire_result* results, hipStream_t s);
+int launch_wire_ku_confirm(const tlsgpu_wire_stream* streams, uint32_t n_streams,
+                           const uint8_t* wire, uint32_t max_records, const tlsgpu_record* recs,
+                           const int32_t* status, tlsgpu_wire_result* results, hipStream_t s);
 int launch_fill_synthetic(uint8_t* d_out, uint64_t stride, uint32_t span_len,
                           uint32_t n, uint64_t seed, uint64_t index0, hipStream_t s);
 int launch_upload_session(const void* img, DevSession* sess, DevGcmTables* tab,

@@ -323,7 +323,7 @@ __global__ __launch_bounds__(64 * kFrameWaves) void wire_frame_kernel(
     r.consumed = walk.consumed;
     r.alert = walk.alert;
     r.alert_record = n;
-    r.reserved[0] = r.reserved[1] = 0;
+    r.key_update = r.reserved = 0;
     results[s] = r;
   }
 }
