@@ -392,8 +392,23 @@ int tlsgpu_group_sync(tlsgpu_group *g);
  * reference reads on, s3_pkt.c:486-488).
  *
  * max_records bounds d_recs / d_status; streams whose records do not fit are
- * truncated at a record boundary (their `records`/`consumed` say how far).
- * d_total receives the number of descriptors written.  Asynchronous.
+ * truncated at a record boundary (their `records`/`consumed` say how far; a
+ * truncated stream reaches no header alert, and its delivered / alert /
+ * alert_record come from the records it kept).  A stream's slots are one
+ * contiguous range, but the ranges are handed out in no fixed order once the
+ * call has more than four streams: read `first`, do not compute it.  A stream
+ * without records reports first = 0.
+ * d_total receives the number of records the streams framed, whether or not
+ * their descriptors fit: it may exceed max_records, and then min(d_total,
+ * max_records) descriptors were written.  Slots no stream got hold all-ones
+ * descriptors and the status TLSGPU_REC_PUBLIC_INVALID.
+ * d_wire: the call writes plaintext spans only (fragment + explicit nonce, the
+ * fragment's length minus explicit nonce and tag): the plaintext of a record
+ * the AEAD accepted (one above 16384 B too), zeros for TLSGPU_REC_BAD_MAC.
+ * The plaintext span of a TLSGPU_REC_SKIPPED record is unspecified (opened,
+ * zeroed or untouched); every other byte of d_wire (headers, explicit nonces,
+ * tags, incomplete tails, the bytes between streams) is never written.
+ * Asynchronous.
  *
  * Streams of a TLS 1.3 table, AES-GCM and ChaCha20-Poly1305 sessions alike
  * (the caller passes version = 0x0303, the legacy
@@ -416,7 +431,7 @@ typedef struct tlsgpu_wire_stream {
 } tlsgpu_wire_stream;
 
 typedef struct tlsgpu_wire_result {
-	uint32_t first;		/* index of the stream's first record in d_recs / d_status */
+	uint32_t first;		/* index of the stream's first record in d_recs / d_status; 0 if none */
 	uint32_t records;	/* records framed (descriptors written) */
 	uint32_t delivered;	/* records before the first failure */
 	uint32_t consumed;	/* bytes of the framed records (header + fragment) */
@@ -579,9 +594,24 @@ int tlsgpu_gather_wire(tlsgpu_sessions *t,
  * numbers run seq, seq + 1, ... (t1_enc.c:258-266).  The sealed records also
  * get descriptors in d_recs (slots reserved per stream, like tlsgpu_open_wire;
  * streams that do not fit max_records are cut at a record boundary) and a
- * status each.  data_bytes / wire_bytes bound the buffers
- * (TLSGPU_REC_OUT_OF_BOUNDS).  tlsgpu_seal_wire_size gives a stream's wire
- * bytes.  Asynchronous.
+ * status each (explicit nonce + fragment + tag bytes for a sealed record).
+ * d_total receives the number of record slots the streams asked for, each
+ * stream's count first capped at max_records: it may exceed max_records, and
+ * then min(d_total, max_records) descriptors were written.  The ranges are
+ * handed out in no fixed order once the call has more than 64 streams; a
+ * stream without records (data_len 0, an unknown or never-installed session,
+ * or cut to nothing: then not a byte of it is written, wire_len is 0 and
+ * next_seq is seq) reports first = 0.  Slots no stream got hold all-ones
+ * descriptors and the status TLSGPU_REC_PUBLIC_INVALID.
+ * data_bytes / wire_bytes bound the buffers, per record: a record's header is
+ * written iff header and fragment lie inside wire_bytes; its fragment is
+ * written iff they do and its plaintext lies inside data_bytes, otherwise the
+ * record's status is TLSGPU_REC_OUT_OF_BOUNDS and not a byte of the fragment
+ * changes.  `records`, wire_len and next_seq count such a record all the same,
+ * so the stream's later records keep their places.  Offsets are 64-bit and do
+ * not wrap: a descriptor offset that would pass 2^64 - 1 stays there (outside
+ * every buffer).  tlsgpu_seal_wire_size gives a stream's wire bytes.
+ * Asynchronous.
  * A TLS 1.3 session of any kind: each fragment (<= max_fragment <= 16384) goes out as the
  * header 17 03 03 BE16(inner + 16) and ciphertext(content || type || zeros) ||
  * tag, inner = the fragment's padded inner plaintext under the session's
@@ -600,7 +630,7 @@ typedef struct tlsgpu_write_stream {
 } tlsgpu_write_stream;
 
 typedef struct tlsgpu_write_result {
-	uint32_t first;		/* index of the stream's first record in d_recs / d_status */
+	uint32_t first;		/* index of the stream's first record in d_recs / d_status; 0 if none */
 	uint32_t records;	/* records written */
 	uint64_t wire_len;	/* bytes written from wire_off (headers + fragments) */
 	uint64_t next_seq;	/* the write sequence number after the last record */

@@ -416,7 +416,7 @@ __global__ __launch_bounds__(256) void wire_seal_frame_kernel(
   const uint32_t first = nrec ? slot0 : 0u;
   if (first >= max_records) nrec = 0;
   else if ((uint64_t)first + nrec > max_records) nrec = max_records - first;
-  res.first = first;
+  res.first = nrec ? first : 0u;  // a stream without records: 0, as wire_frame_kernel has it
   if (nrec) {
     const DevSession& S = sessions[st.session];
     // TLS 1.3 (tls13_session: GCM or ChaCha): the fragment is content || inner type ||
@@ -425,12 +425,16 @@ __global__ __launch_bounds__(256) void wire_seal_frame_kernel(
     const bool t13 = tls13_session(S.kind, S.nonce_in_record);
     const uint32_t pad_mask = S.pad_mask;
     const uint32_t over = (S.nonce_in_record ? 8u : 0u) + S.tag_len;  // eivlen + tag
+    // offsets saturate at 2^64 - 1 (outside every buffer) instead of wrapping back
+    // into one: a wire_off / data_off near 2^64 must not land a record at its start
+    auto sat_add = [](uint64_t x, uint64_t y) { return x + y < x ? ~0ull : x + y; };
     uint64_t pos = st.wire_off;
+    bool wrapped = false;  // pos left 64 bits: no later record of the stream lies in the wire
     for (uint32_t k = 0; k < nrec; k++) {
       const uint32_t len = min(frag, st.data_len - k * frag);
       // the length field (s3_pkt.c:733)
       const uint32_t L = (t13 ? tls13_inner_len(len, pad_mask) : len) + over;
-      if (pos <= wire_bytes && (uint64_t)kHdr + L <= wire_bytes - pos) {  // no wrap
+      if (!wrapped && pos <= wire_bytes && (uint64_t)kHdr + L <= wire_bytes - pos) {  // no wrap
         uint8_t* h = wire + pos;
         h[0] = t13 ? (uint8_t)kAppData : st.type;
         h[1] = t13 ? 3 : (uint8_t)(st.version >> 8);
@@ -439,13 +443,14 @@ __global__ __launch_bounds__(256) void wire_seal_frame_kernel(
         h[4] = (uint8_t)L;
       }
       tlsgpu_record d;
-      d.in_off = st.data_off + (uint64_t)k * frag;
-      d.out_off = pos + kHdr;
+      d.in_off = sat_add(st.data_off, (uint64_t)k * frag);
+      d.out_off = wrapped ? ~0ull : sat_add(pos, kHdr);
       d.seq = st.seq + k;
       d.session = st.session;
       d.len_type = TLSGPU_LEN_TYPE(len, st.type);
       recs[first + k] = d;
-      pos += kHdr + L;
+      wrapped = wrapped || pos + kHdr + L < pos;
+      pos += kHdr + L;  // (wire_len stays the records' bytes, modulo 2^64)
     }
     res.records = nrec;
     res.wire_len = pos - st.wire_off;

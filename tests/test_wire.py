@@ -92,27 +92,37 @@ def model_stream(oracle, osess, kind, wire, version, first_packet, rbuf_len, seq
     return out, consumed, alert, alert_rec, delivered
 
 
-def build_streams(oracle, ta, rnd, kind):
-    """Good, tampered, malformed and truncated streams of one AEAD kind."""
+def make_session(oracle, ta, rnd, kind):
+    """(SessionParams, the oracle's session) of one AEAD kind with keys from rnd."""
     key = bytes(rnd.randrange(256) for _ in range(po.KEY_LEN[kind]))
     fiv = bytes(rnd.randrange(256) for _ in range(po.FIXED_IV_LEN[kind]))
-    params = ta.SessionParams(kind, key, fiv)
-    osess = oracle.tls_session(kind, key, fiv)
+    return ta.SessionParams(kind, key, fiv), oracle.tls_session(kind, key, fiv)
+
+
+def build_streams(oracle, rnd, osess, session=0, big=True, overflow=None):
+    """Good, tampered, malformed and truncated streams under one session (osess: its
+    oracle session, `session` its id in the table; the last stream names session 7,
+    which its table does not have).  test_gpu_wire_image.py repeats the shapes
+    many times and shortens them: big=False makes the good 16 KiB record of the
+    first stream 517 bytes; overflow=False (default: as `big`) takes the long
+    fragment from the two shapes that need one, which then are a garbage record
+    (bad_record_mac) and three good records instead of two record_overflows."""
+    overflow = big if overflow is None else overflow
 
     def rec(seq, n, rtype=23, version=TLS12):
         pt = bytes(rnd.randrange(256) for _ in range(n))
         body = oracle.tls_seal(osess, seq, rtype, pt)
         return header(rtype, version, len(body)) + body
 
-    def stream(parts, seq0, version=TLS12, first_packet=False, rbuf_len=0, session=0):
+    def stream(parts, seq0, version=TLS12, first_packet=False, rbuf_len=0, session=session):
         return dict(wire=b"".join(parts), seq=seq0, version=version, first=first_packet,
                     rbuf=rbuf_len, session=session)
 
     S = []
     q = rnd.randrange(1 << 40)
     # good records of mixed lengths + 3 trailing bytes of the next header
-    S.append(stream([rec(q, 0), rec(q + 1, 1), rec(q + 2, 1400), rec(q + 3, 16384), rec(q + 4, 7),
-                     header(23, TLS12, 100)[:3]], q))
+    S.append(stream([rec(q, 0), rec(q + 1, 1), rec(q + 2, 1400), rec(q + 3, 16384 if big else 517),
+                     rec(q + 4, 7), header(23, TLS12, 100)[:3]], q))
     # tampered 4th record: bad_record_mac, the rest skipped
     q = rnd.randrange(1 << 40)
     parts = [rec(q + i, rnd.randrange(1, 3000)) for i in range(6)]
@@ -133,12 +143,13 @@ def build_streams(oracle, ta, rnd, kind):
     # length above rbuf: overflow at the header even without the fragment
     S.append(stream([header(23, TLS12, 16708) + bytes(10)], 0))
     # 16704 < length <= rbuf - 5, full fragment: overflow after the read
-    S.append(stream([header(23, TLS12, 16705) + bytes(16705)], 0))
+    S.append(stream([header(23, TLS12, 16705) + bytes(16705)] if overflow else
+                    [header(23, TLS12, 305) + bytes(305)], 0))
     # fragment shorter than explicit nonce + tag: decryption_failed
     S.append(stream([rec(9, 5), header(23, TLS12, 10) + bytes(10)], 9))
     # plaintext longer than 16384 (fragment within 16704): record_overflow
     q = rnd.randrange(1 << 40)
-    S.append(stream([rec(q, 100), rec(q + 1, 16400), rec(q + 2, 10)], q))
+    S.append(stream([rec(q, 100), rec(q + 1, 16400 if overflow else 164), rec(q + 2, 10)], q))
     # the last record's fragment is incomplete: framed up to it
     q = rnd.randrange(1 << 40)
     last = rec(q + 2, 900)
@@ -148,7 +159,7 @@ def build_streams(oracle, ta, rnd, kind):
     S.append(stream([rec(q, 100), rec(q + 1, 2000)], q, rbuf_len=1024))
     # unknown session: framed, publicly invalid -> decryption_failed
     S.append(stream([rec(5, 10)], 5, session=7))
-    return params, osess, S
+    return S
 
 
 def run_wire(ta, engine, table, streams, max_records):
@@ -186,7 +197,8 @@ def run_wire(ta, engine, table, streams, max_records):
                                   po.CHACHA20_POLY1305_OLD])
 def test_open_wire_matches_ssl3_get_record(ta, engine, oracle, kind):
     rnd = random.Random(100 + kind)
-    params, osess, streams = build_streams(oracle, ta, rnd, kind)
+    params, osess = make_session(oracle, ta, rnd, kind)
+    streams = build_streams(oracle, rnd, osess)
     table = ta.SessionTable(engine, 1)
     table.install(0, [params])
     got = run_wire(ta, engine, table, streams, max_records=256)
