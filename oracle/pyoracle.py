@@ -178,6 +178,56 @@ class Oracle:
         return bytes(mac)
 
 
+class GcmStream:
+    """One GCM128_CONTEXT fed piecewise (CRYPTO_gcm128_setiv / _aad / _encrypt /
+    _decrypt / _tag / _finish, gcm128.c:749-1521) over liboracle.so: the state
+    lives across calls and every call returns gcm128.c's return code."""
+
+    def __init__(self, oracle: Oracle, key: bytes):
+        self.lib = oracle.lib
+        ks = (C.c_ubyte * 256)()
+        self.lib.oracle_aes_set_encrypt_key(_buf(key), len(key) * 8, ks)
+        self.g = (C.c_ubyte * 2048)()   # oracle_gcm_ctx holds its own copy of the key schedule
+        self.lib.oracle_gcm_init(self.g, ks)
+
+    def copy(self) -> "GcmStream":
+        other = GcmStream.__new__(GcmStream)
+        other.lib = self.lib
+        other.g = (C.c_ubyte * 2048).from_buffer_copy(self.g)
+        return other
+
+    def setiv(self, iv: bytes) -> None:
+        self.lib.oracle_gcm_setiv(self.g, _buf(iv), len(iv))
+
+    def aad(self, data: bytes) -> int:
+        return self.lib.oracle_gcm_aad(self.g, _buf(data), len(data))
+
+    def _crypt(self, fn, data: bytes):
+        out = (C.c_ubyte * max(len(data), 1))()
+        rc = fn(self.g, _buf(data), out, len(data))
+        return rc, bytes(out)[:len(data)]
+
+    def encrypt(self, data: bytes):
+        """(rc, ciphertext)"""
+        return self._crypt(self.lib.oracle_gcm_encrypt, data)
+
+    def decrypt(self, data: bytes):
+        """(rc, plaintext)"""
+        return self._crypt(self.lib.oracle_gcm_decrypt, data)
+
+    def tag(self, n: int = 16) -> bytes:
+        """CRYPTO_gcm128_tag; on a copy of the state (oracle_gcm_tag folds the
+        lengths into Xi), so the stream can go on."""
+        t = (C.c_ubyte * 16)()
+        self.lib.oracle_gcm_tag(self.copy().g, t, 16)
+        return bytes(t)[:n]
+
+    def finish(self, tag: bytes) -> int:
+        """CRYPTO_gcm128_finish: 0 when the first len(tag) <= 16 bytes agree;
+        -1 stands for gcm128.c's non-zero memcmp value and its -1."""
+        return 0 if 0 < len(tag) <= 16 and self.tag(len(tag)) == tag else -1
+
+
 class _EvpCtx(C.Structure):
     _fields_ = [("aead", C.c_void_p), ("aead_state", C.c_void_p)]
 

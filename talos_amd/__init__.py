@@ -13,7 +13,9 @@ interface for the batch path:
 * :func:`open_batch` / :func:`seal_batch` — ``tls1_enc(s, 0/1)``'s AEAD branch
   (ssl/t1_enc.c:832-975) over a device-resident array of records;
 * :class:`EvpAead` — the per-call ``EVP_AEAD_CTX_*`` functions of
-  crypto/evp/evp_aead.c as exported by libtlsgpu.so.
+  crypto/evp/evp_aead.c as exported by libtlsgpu.so;
+* :class:`EvpCipher` — an ``EVP_CIPHER_CTX`` on the ``EVP_aes_{128,256}_gcm``
+  objects (the GCM128 stream kernel), driven as crypto/evp/evp_enc.c does.
 
 There is no CPU fallback: if the shared library is missing or no GPU is
 present the calls raise :class:`TlsGpuError`.
@@ -765,6 +767,128 @@ class EvpAead:
 
     def cleanup(self) -> None:
         self.lib.EVP_AEAD_CTX_cleanup(C.byref(self.ctx))
+
+
+class _EvpCipherCtx(C.Structure):
+    pass
+
+
+class _EvpCipher(C.Structure):
+    """struct evp_cipher_st (include/tlsgpu_evp.h, evp.h:297-313)"""
+    _fields_ = [("nid", C.c_int), ("block_size", C.c_int), ("key_len", C.c_int),
+                ("iv_len", C.c_int), ("flags", C.c_ulong),
+                ("init", C.CFUNCTYPE(C.c_int, C.POINTER(_EvpCipherCtx), C.c_void_p, C.c_void_p,
+                                     C.c_int)),
+                ("do_cipher", C.CFUNCTYPE(C.c_int, C.POINTER(_EvpCipherCtx), C.c_void_p,
+                                          C.c_void_p, C.c_size_t)),
+                ("cleanup", C.CFUNCTYPE(C.c_int, C.POINTER(_EvpCipherCtx))),
+                ("ctx_size", C.c_int), ("set_asn1_parameters", C.c_void_p),
+                ("get_asn1_parameters", C.c_void_p),
+                ("ctrl", C.CFUNCTYPE(C.c_int, C.POINTER(_EvpCipherCtx), C.c_int, C.c_int,
+                                     C.c_void_p)),
+                ("app_data", C.c_void_p)]
+
+
+# struct evp_cipher_ctx_st (include/tlsgpu_evp.h, evp.h:405-423)
+_EvpCipherCtx._fields_ = [("cipher", C.POINTER(_EvpCipher)), ("engine", C.c_void_p),
+                          ("encrypt", C.c_int), ("buf_len", C.c_int), ("oiv", C.c_ubyte * 16),
+                          ("iv", C.c_ubyte * 16), ("buf", C.c_ubyte * 32), ("num", C.c_int),
+                          ("app_data", C.c_void_p), ("key_len", C.c_int), ("flags", C.c_ulong),
+                          ("cipher_data", C.c_void_p), ("final_used", C.c_int),
+                          ("block_mask", C.c_int), ("final", C.c_ubyte * 32)]
+
+
+class EvpCipher:
+    """EVP_CIPHER_CTX over the EVP_aes_{128,256}_gcm objects of libtlsgpu.so,
+    driven the way a generic EVP layer (crypto/evp/evp_enc.c) drives a
+    custom-cipher object: cipher_data of ctx_size bytes, ctrl(INIT), init(key,
+    iv, enc), update = do_cipher(out, in, len), final = do_cipher(out, NULL, 0),
+    copy = struct copy + fresh cipher_data + ctrl(COPY).  Every method returns
+    what the object's function returned."""
+
+    CTRL_INIT, CTRL_COPY, GCM_SET_IVLEN, GCM_GET_TAG, GCM_SET_TAG = 0x0, 0x8, 0x9, 0x10, 0x11
+    GCM_SET_IV_FIXED, GCM_IV_GEN, AEAD_TLS1_AAD, GCM_SET_IV_INV = 0x12, 0x13, 0x16, 0x18
+    GETTERS = {AES_128_GCM: "EVP_aes_128_gcm", AES_256_GCM: "EVP_aes_256_gcm"}
+
+    def __init__(self, kind: int, enc: bool):
+        """EVP_CipherInit_ex(ctx, cipher, NULL, NULL, NULL, enc)"""
+        self.lib = load_library()
+        getter = getattr(self.lib, self.GETTERS[kind])
+        getter.restype = C.POINTER(_EvpCipher)
+        self.cipher = getter().contents
+        self.ctx = _EvpCipherCtx()
+        self.ctx.cipher = C.pointer(self.cipher)
+        self.ctx.encrypt = int(bool(enc))
+        self.ctx.key_len = self.cipher.key_len
+        self.ctx.block_mask = self.cipher.block_size - 1
+        self._data = (C.c_ubyte * self.cipher.ctx_size)()
+        self.ctx.cipher_data = C.addressof(self._data)
+        self.ok = self.cipher.ctrl(C.byref(self.ctx), self.CTRL_INIT, 0, None)
+
+    def init(self, key: bytes | None = None, iv: bytes | None = None) -> int:
+        """EVP_CipherInit_ex(ctx, NULL, NULL, key, iv, enc): the object's init."""
+        return self.cipher.init(C.byref(self.ctx), EvpAead._b(key), EvpAead._b(iv),
+                                self.ctx.encrypt)
+
+    def ctrl(self, kind: int, arg: int, ptr=None) -> int:
+        """EVP_CIPHER_CTX_ctrl; ptr: None, a ctypes buffer (written in place) or bytes."""
+        if isinstance(ptr, (bytes, bytearray)):
+            ptr = EvpAead._b(bytes(ptr))
+        return self.cipher.ctrl(C.byref(self.ctx), kind, arg, ptr)
+
+    def get_tag(self, n: int = 16):
+        """(rc, tag) of EVP_CTRL_GCM_GET_TAG"""
+        t = (C.c_ubyte * 16)()
+        rc = self.ctrl(self.GCM_GET_TAG, n, t)
+        return rc, bytes(t)[:n]
+
+    def do_cipher(self, out: int | None, inp: int | None, n: int) -> int:
+        """The object's do_cipher on raw addresses (EVP_Cipher)."""
+        return self.cipher.do_cipher(C.byref(self.ctx), out, inp, n)
+
+    def update(self, data: bytes):
+        """(rc, output) of EVP_CipherUpdate(out, in, len) out of place."""
+        out, src = (C.c_ubyte * max(len(data), 1))(), EvpAead._b(data)
+        rc = self.do_cipher(C.addressof(out), C.addressof(src), len(data))
+        return rc, bytes(out)[:len(data)]
+
+    def update_aad(self, data: bytes) -> int:
+        """EVP_CipherUpdate(NULL, in, len): AAD."""
+        src = EvpAead._b(data)
+        return self.do_cipher(None, C.addressof(src), len(data))
+
+    def final(self) -> int:
+        """EVP_CipherFinal_ex: do_cipher(out, NULL, 0)"""
+        out = (C.c_ubyte * 32)()
+        return self.do_cipher(C.addressof(out), None, 0)
+
+    def copy(self) -> "EvpCipher":
+        """EVP_CIPHER_CTX_copy (evp_enc.c): the struct and cipher_data copied,
+        then the source's ctrl(COPY) with the new context."""
+        other = EvpCipher.__new__(EvpCipher)
+        other.lib, other.cipher = self.lib, self.cipher
+        other.ctx = _EvpCipherCtx()
+        C.memmove(C.byref(other.ctx), C.byref(self.ctx), C.sizeof(_EvpCipherCtx))
+        other._data = (C.c_ubyte * self.cipher.ctx_size).from_buffer_copy(self._data)
+        other.ctx.cipher_data = C.addressof(other._data)
+        other.ok = self.cipher.ctrl(C.byref(self.ctx), self.CTRL_COPY, 0, C.byref(other.ctx))
+        return other
+
+    def cleanup(self) -> int:
+        """EVP_CIPHER_CTX_cleanup: the object's cleanup, then cipher_data is dropped."""
+        if not self.ctx.cipher_data:
+            return 1
+        rc = self.cipher.cleanup(C.byref(self.ctx))
+        self.ctx.cipher_data = None
+        return rc
+
+
+def evp_cipher_stats() -> int:
+    """GCM128 step programs the EVP_CIPHER objects have run on the GPU
+    (tlsgpu_evp_cipher_stats)."""
+    n = C.c_uint64(0)
+    _check(load_library().tlsgpu_evp_cipher_stats(C.byref(n)), "tlsgpu_evp_cipher_stats")
+    return n.value
 
 
 def evp_set_batching(window_us: int, max_jobs: int = 0, pool_sessions: int = 0) -> None:

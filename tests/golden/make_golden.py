@@ -31,9 +31,14 @@ Inputs (read-only, never copied as source):
     trace goes to batch_plan_trace.json.  Record it from the sources whose
     launches are to be kept (before a change to run_batch), never after.
 
+  * --ctr-wrap (and the full run): oracle/_ref/libref.so seals a dozen
+    EVP_AEAD jobs on the crafted IVs of tests/gcm_iv_craft.py, whose 32-bit
+    block counter wraps or crosses 2^16 / 2^24 inside the job; inputs and
+    output digests go to gcm_ctr_wrap.json.
+
 Outputs: aeadtests.txt, gcm128_vectors.json, chacha_vectors.json,
-poly1305_vectors.json, records.json, batch_digests.json, wire_ref.json,
-batch_plan_trace.json (--batch-plan only).
+poly1305_vectors.json, records.json, gcm_ctr_wrap.json, batch_digests.json,
+wire_ref.json, batch_plan_trace.json (--batch-plan only).
 """
 from __future__ import annotations
 
@@ -147,6 +152,41 @@ def make_records(ref: po.Reference):
                 rec["body"] = body.hex()
             recs.append(rec)
     return recs
+
+
+# ids of tests/gcm_iv_craft.py wrap_cases() kept as reference outputs, key sizes in turn
+CTR_WRAP_IDS = ["n0-w0", "n16-w0", "n17-w1", "n100-w6", "n16384-w0", "n16384-w64",
+                "n16384-w1023", "n16389-w128", "n16389-w1024", "n33801-w81", "n33801-w145",
+                "n16384-ctr0000fff0", "n16384-ctr00ffffc0"]
+
+
+def make_ctr_wrap(ref: po.Reference):
+    """EVP_AEAD seals by the reference on IVs whose 32-bit block counter wraps
+    (or crosses 2^16 / 2^24) inside the job: inputs and a digest of each output."""
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import gcm_iv_craft as gic
+    orc = po.Oracle()
+    cases = gic.wrap_cases()
+    out = []
+    for k, cid in enumerate(CTR_WRAP_IDS):
+        index = [c["id"] for c in cases].index(cid)
+        case = cases[index]
+        key_len = gic.KEY_LENS[k % 2]
+        key, iv, aad, pt = gic.case_inputs(orc, case, key_len, index)
+        kind = po.AES_128_GCM if key_len == 16 else po.AES_256_GCM
+        ctx = ref.aead(kind, key, case["tag_len"])
+        ok, sealed = ref.seal(ctx, iv, pt, aad)
+        assert ok == 1 and ref.open(ctx, iv, sealed, aad) == (1, pt)
+        out.append({"id": f"{cid}-k{key_len * 8}", "w": case["w"], "j0_ctr": case["j0_ctr"],
+                    "key": key.hex(), "iv": iv.hex(), "aad": aad.hex(),
+                    "tag_len": case["tag_len"], "pt_seed": gic.case_seed(index, key_len),
+                    "pt_index": 3, "pt_len": len(pt), "sealed_len": len(sealed),
+                    "sealed_sha256": hashlib.sha256(sealed).hexdigest(),
+                    "first32": sealed[:32].hex(), "last32": sealed[-32:].hex()})
+    return {"generator": "tests/golden/make_golden.py --ctr-wrap via oracle/_ref/libref.so",
+            "plaintext": "gcm_iv_craft.fill(pt_seed, pt_index, pt_len): the SplitMix64 stream "
+                         "of oracle_fill_bytes",
+            "cases": out}
 
 
 # name: (aead, records, sessions, seed, tamper_every, length or "zipf")
@@ -265,6 +305,11 @@ def main():
     if len(sys.argv) > 1 and sys.argv[1] == "--wire":
         json.dump(make_wire_ref(), open(os.path.join(HERE, "wire_ref.json"), "w"))
         return
+    if len(sys.argv) > 1 and sys.argv[1] == "--ctr-wrap":
+        po.build()
+        json.dump(make_ctr_wrap(po.Reference()),
+                  open(os.path.join(HERE, "gcm_ctr_wrap.json"), "w"), indent=1)
+        return
     if len(sys.argv) > 2 and sys.argv[1] == "--digests":
         # recompute only the named batch digests and merge them into the fixture
         path = os.path.join(HERE, "batch_digests.json")
@@ -285,6 +330,7 @@ def main():
     json.dump({"generator": "tests/golden/make_golden.py via oracle/_ref/libref.so",
                "records": make_records(ref)},
               open(os.path.join(HERE, "records.json"), "w"), indent=1)
+    json.dump(make_ctr_wrap(ref), open(os.path.join(HERE, "gcm_ctr_wrap.json"), "w"), indent=1)
     json.dump({"generator": "tests/golden/make_golden.py via oracle/_ref/batch_digest "
                             "(reference libcrypto, oracle/_ref/libssl_ref.so)",
                "batches": make_batch_digests()},

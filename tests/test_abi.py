@@ -45,6 +45,29 @@ def test_aead_descriptors_without_gpu(lib):
         assert got == want[kind]
 
 
+def test_evp_cipher_objects_without_gpu(lib):
+    """EvpCipher's ctypes layouts against the EVP_aes_*_gcm objects (e_aes.c:1049-1059):
+    the fields read back, and the ctrls that need no key run on the host alone."""
+    import talos_amd as ta
+    E = ta.EvpCipher
+    for kind, nid, key_len in ((ta.AES_128_GCM, 895, 16), (ta.AES_256_GCM, 901, 32)):
+        c = E(kind, False)
+        ci = c.cipher
+        assert c.ok == 1
+        assert (ci.nid, ci.block_size, ci.key_len, ci.iv_len) == (nid, 1, key_len, 12)
+        assert ci.flags & 0x7 == 0x6 and ci.flags & 0x200000 and 0 < ci.ctx_size <= 4096
+        assert c.ctx.key_len == key_len and c.ctx.encrypt == 0
+        assert c.ctrl(E.GCM_SET_IVLEN, 0) == 0 and c.ctrl(E.GCM_SET_IVLEN, 60) == 1
+        assert c.ctrl(E.GCM_SET_TAG, 17, bytes(17)) == 0
+        assert c.ctrl(E.GCM_SET_TAG, 12, bytes(range(12))) == 1
+        assert bytes(c.ctx.buf)[:12] == bytes(range(12))
+        assert c.get_tag(16)[0] == 0          # a decrypting context gives no tag
+        assert c.update(b"x")[0] == -1        # no key yet
+        d = c.copy()                          # nothing on the device to copy yet
+        assert d.ok == 1 and d.ctx.cipher_data != c.ctx.cipher_data
+        assert d.cleanup() == 1 and c.cleanup() == 1 and c.cleanup() == 1
+
+
 def test_record_descriptor_layout():
     import talos_amd as ta
     import numpy as np
