@@ -199,6 +199,74 @@ void tlsgpu_sessions_destroy(tlsgpu_sessions *t);
 int tlsgpu_sessions_install(tlsgpu_sessions *t, uint32_t first, uint32_t n,
     const tlsgpu_session_params *params);
 
+/* ---------------------------------------------------------------------------
+ * The TLS 1.3 key schedule behind a traffic secret, on the device (RFC 8446
+ * 7.1-7.3).
+ *
+ * A TLS 1.3 session given as its traffic secret (client/server
+ * application_traffic_secret_N).  The hash of the key schedule follows from the
+ * suite (RFC 8446 B.4): SHA-256 for TLSGPU_AES_128_GCM and
+ * TLSGPU_CHACHA20_POLY1305_TLS13 (secret_len 32), SHA-384 for
+ * TLSGPU_AES_256_GCM (secret_len 48).  Any other kind or a secret_len that does
+ * not match is TLSGPU_EINVAL.  pad_block as in tlsgpu_session_params.  version
+ * is implied (0x0304), tag 16, IV 12. */
+typedef struct tlsgpu_secret_params {
+	int32_t  aead;
+	uint32_t secret_len;
+	uint8_t  secret[48];
+	uint16_t pad_block;
+	uint16_t reserved;     /* 0 */
+} tlsgpu_secret_params;    /* 60 bytes */
+
+/* Install n sessions from their traffic secrets at ids first..first+n-1.
+ * Synchronous and host-visible like tlsgpu_sessions_install, with its range
+ * check, its one-generation-per-table rule (this is a TLS 1.3 install: on a
+ * TLS 1.2 table it is TLSGPU_EINVAL) and its pad_block check; everything is
+ * checked before the first GPU call.  The device derives
+ *   key = HKDF-Expand-Label(secret, "key", "", key_len)
+ *   iv  = HKDF-Expand-Label(secret, "iv", "", 12)
+ * and installs the slot exactly as tlsgpu_sessions_install would for those
+ * bytes; the slot also keeps the secret, which is what lets
+ * tlsgpu_sessions_key_update move it on.  The staging copy of the secrets in
+ * device memory is zeroed before the call returns, and no key or secret
+ * travels as a kernel argument.  A later tlsgpu_sessions_install over the slot
+ * clears its secret.  The first call allocates the table's key-schedule scratch
+ * (8 MiB and 4 bytes per session of capacity), freed with the table.
+ * It must not overlap a tlsgpu_sessions_key_update of the same table that is
+ * still running on another stream (the two share the scratch). */
+int tlsgpu_sessions_install_secrets(tlsgpu_sessions *t, uint32_t first, uint32_t n,
+    const tlsgpu_secret_params *params);
+
+/* KeyUpdate (RFC 8446 4.6.3, 7.2) for n session slots, on the device and
+ * asynchronous on `stream` (NULL = engine stream): no host round trip, no
+ * allocation, no synchronising call.  d_ids and d_status are device arrays of
+ * n.  For each i, slot d_ids[i] moves one generation on:
+ *   secret' = HKDF-Expand-Label(secret, "traffic upd", "", Hash.length)
+ * the key and IV come from secret' as above, the slot is installed again (key
+ * schedule, H, GHASH tables, or the ChaCha key; its kind, padding block and
+ * everything else stay) and keeps secret'.
+ *   d_status[i] = TLSGPU_OK             the slot was rekeyed
+ *                 TLSGPU_REKEY_SKIPPED  d_ids[i] == TLSGPU_SESSION_NONE
+ *                 TLSGPU_ERANGE         the id is >= capacity; nothing is touched
+ *                 TLSGPU_EINVAL         the slot holds no secret (empty, or installed
+ *                                       from a key); not one byte of it changes
+ * An id listed several times in one call is rekeyed ONCE (every entry reports
+ * TLSGPU_OK): all derivations read the old generation before any install
+ * writes.  Slots not listed are not touched.  The host's view of the table does
+ * not change (kind and padding stay), so the call takes no lock.
+ * A null table, d_ids or d_status with n > 0 is TLSGPU_EINVAL before any GPU
+ * call; n == 0 is TLSGPU_OK and launches nothing.
+ * Ordering is the caller's, as for installs: the call goes behind the batches
+ * that use the old keys and before those that use the new ones (one stream
+ * does it).  Two tlsgpu_sessions_key_update calls on one table must be ordered
+ * against each other, by using one stream or by waiting for the first: they
+ * share the table's scratch.  Sequence numbers restart at 0 under the new keys;
+ * that is the caller's `seq`, as ever. */
+#define TLSGPU_SESSION_NONE 0xFFFFFFFFu
+#define TLSGPU_REKEY_SKIPPED 1
+int tlsgpu_sessions_key_update(tlsgpu_sessions *t, const uint32_t *d_ids, uint32_t n,
+    int32_t *d_status, void *stream);
+
 /* Batch record decrypt / encrypt (device-resident).  Any record order is
  * correct; grouping each session's records together is fastest.  in_bytes /
  * out_bytes are the sizes of d_in / d_out: records whose spans leave them get
@@ -332,6 +400,10 @@ void tlsgpu_group_sessions_destroy(tlsgpu_group_sessions *gs);
 tlsgpu_sessions *tlsgpu_group_sessions_member(tlsgpu_group_sessions *gs, uint32_t member);
 int tlsgpu_group_sessions_install(tlsgpu_group_sessions *gs, uint32_t first, uint32_t n,
     const tlsgpu_session_params *params);
+/* tlsgpu_sessions_install_secrets on every member.  There is no group-wide
+ * KeyUpdate: run tlsgpu_sessions_key_update on tlsgpu_group_sessions_member(gs, k). */
+int tlsgpu_group_sessions_install_secrets(tlsgpu_group_sessions *gs, uint32_t first,
+    uint32_t n, const tlsgpu_secret_params *params);
 
 /* Byte-balanced contiguous split of n records into `parts` slices: cuts[0] = 0
  * <= cuts[1] <= ... <= cuts[parts] = n, slice k = records [cuts[k], cuts[k+1]).
@@ -484,19 +556,30 @@ typedef struct tlsgpu_wire_result {
  *                                    another type or other content.  Go on from
  *                                    `consumed` under the same keys with seq +
  *                                    records, unless `alert` ended the stream.
- * After TLSGPU_WIRE_KU_UPDATE*: derive application_traffic_secret_N+1 =
- * HKDF-Expand-Label(secret_N, "traffic upd", "", Hash.length) and its key and IV
- * on the host, install them into the stream's read session slot
- * (tlsgpu_sessions_install, between batches as always), and make the next call
- * at wire_off + consumed with seq = 0.  tlsgpu_gather_wire stops at the
- * KeyUpdate record with TLSGPU_READ_NOT_APP_DATA, stop_type 22, stop_len 5.
+ * After TLSGPU_WIRE_KU_UPDATE*: the stream's read session slot moves to
+ * application_traffic_secret_N+1 = HKDF-Expand-Label(secret_N, "traffic upd",
+ * "", Hash.length) and its key and IV, and the next call starts at wire_off +
+ * consumed with seq = 0.  For a slot installed from its traffic secret
+ * (tlsgpu_sessions_install_secrets) the device does it, behind the open on the
+ * same stream and with nothing read back first:
+ *   tlsgpu_open_wire -> tlsgpu_wire_key_update_ids -> tlsgpu_sessions_key_update
+ * (the host still reads `consumed` and key_update before it builds the next
+ * call's streams; it may do so after queuing the rekey).  For a slot installed
+ * from a key the caller derives the next secret, key and IV on the host and
+ * installs them (tlsgpu_sessions_install, between batches as always).
+ * tlsgpu_gather_wire stops at the KeyUpdate record with
+ * TLSGPU_READ_NOT_APP_DATA, stop_type 22, stop_len 5.
  * Limits: a KeyUpdate that follows another handshake message inside one record,
  * or one split over two records, is not seen by the peek; such a stream behaves
  * as with the switch off.  There is no second session per stream: the bytes
  * behind the cut are never opened in the same call (under pre-installed next
- * keys a look-alike would destroy the connection).  The engine derives no
- * traffic secrets and sends no KeyUpdate: the write side is a tlsgpu_seal_wire
- * stream of type 22 with the 5-byte message, then a reinstall of the write slot. */
+ * keys a look-alike would destroy the connection).  The engine derives the
+ * generations that follow an installed traffic secret and nothing before it
+ * (no handshake secrets, no application_traffic_secret_0 from the master
+ * secret), and it sends no KeyUpdate by itself: the write side is a
+ * tlsgpu_seal_wire stream of type 22 with the 5-byte message, then
+ * tlsgpu_sessions_key_update of the write slot on the same stream (or a
+ * reinstall of a slot installed from a key). */
 #define TLSGPU_WIRE_KU_NONE 0
 #define TLSGPU_WIRE_KU_UPDATE 1
 #define TLSGPU_WIRE_KU_UPDATE_REQUESTED 2
@@ -506,6 +589,17 @@ int tlsgpu_sessions_wire_key_update(tlsgpu_sessions *t, int on);
 int tlsgpu_open_wire(tlsgpu_sessions *t, const tlsgpu_wire_stream *d_streams,
     uint32_t n_streams, uint8_t *d_wire, uint32_t max_records, tlsgpu_record *d_recs,
     int32_t *d_status, tlsgpu_wire_result *d_results, uint32_t *d_total, void *stream);
+
+/* The id list tlsgpu_sessions_key_update takes, from the results of a
+ * tlsgpu_open_wire with the KeyUpdate switch on; asynchronous on `stream`,
+ * ordered behind that open.  For each stream i:
+ *   d_ids[i] = d_streams[i].session  d_results[i].key_update is
+ *                                    TLSGPU_WIRE_KU_UPDATE or _UPDATE_REQUESTED
+ *   d_ids[i] = TLSGPU_SESSION_NONE   otherwise (TLSGPU_WIRE_KU_NONE, _HELD)
+ * d_ids is a device array of n_streams.  A null argument with n_streams > 0 is
+ * TLSGPU_EINVAL; n_streams == 0 is TLSGPU_OK and launches nothing. */
+int tlsgpu_wire_key_update_ids(tlsgpu_sessions *t, const tlsgpu_wire_stream *d_streams,
+    const tlsgpu_wire_result *d_results, uint32_t n_streams, uint32_t *d_ids, void *stream);
 
 /* ---------------------------------------------------------------------------
  * Wire read path: ssl3_read_bytes (ssl/s3_pkt.c:840-1130) for many connections.

@@ -126,6 +126,36 @@ class SessionParams:
         return p
 
 
+class _SecretParams(C.Structure):
+    _fields_ = [("aead", C.c_int32), ("secret_len", C.c_uint32), ("secret", C.c_uint8 * 48),
+                ("pad_block", C.c_uint16), ("reserved", C.c_uint16)]
+
+
+# tlsgpu_sessions_key_update: an id that names no slot, and its status
+SESSION_NONE, REKEY_SKIPPED = 0xFFFFFFFF, 1
+
+
+@dataclass
+class SecretParams:
+    """A TLS 1.3 session given as its traffic secret (tlsgpu_secret_params): 32
+    bytes for AES_128_GCM and CHACHA20_POLY1305_TLS13 (SHA-256), 48 for
+    AES_256_GCM (SHA-384).  The device derives the key and the IV."""
+    aead: int
+    secret: bytes
+    pad_block: int = 0
+
+    def to_c(self) -> _SecretParams:
+        p = _SecretParams()
+        p.aead = self.aead
+        p.secret_len = len(self.secret)
+        if len(self.secret) > 48:
+            raise ValueError("a traffic secret has at most 48 bytes")
+        if self.secret:
+            C.memmove(p.secret, self.secret, len(self.secret))
+        p.pad_block = self.pad_block
+        return p
+
+
 def build(quiet: bool = True) -> None:
     """Compile libtlsgpu.so for gfx950 in-tree (hipcc)."""
     subprocess.run(["make", "-C", HERE, "-j8"], check=True,
@@ -154,6 +184,9 @@ def load_library(path: str = LIBPATH) -> C.CDLL:
         "tlsgpu_sessions_create": (i32, [vp, u32, C.POINTER(vp)]),
         "tlsgpu_sessions_destroy": (None, [vp]),
         "tlsgpu_sessions_install": (i32, [vp, u32, u32, vp]),
+        "tlsgpu_sessions_install_secrets": (i32, [vp, u32, u32, vp]),
+        "tlsgpu_sessions_key_update": (i32, [vp, vp, u32, vp, vp]),
+        "tlsgpu_wire_key_update_ids": (i32, [vp, vp, vp, u32, vp, vp]),
         "tlsgpu_sessions_hint": (i32, [vp, u32]),
         "tlsgpu_sessions_wire_key_update": (i32, [vp, i32]),
         "tlsgpu_open_batch": (i32, [vp, vp, u32, vp, C.c_size_t, vp, C.c_size_t, vp, vp]),
@@ -220,6 +253,7 @@ def load_library(path: str = LIBPATH) -> C.CDLL:
         "tlsgpu_group_sessions_destroy": (None, [vp]),
         "tlsgpu_group_sessions_member": (vp, [vp, u32]),
         "tlsgpu_group_sessions_install": (i32, [vp, u32, u32, vp]),
+        "tlsgpu_group_sessions_install_secrets": (i32, [vp, u32, u32, vp]),
         "tlsgpu_split_by_bytes": (i32, [vp, u32, u32, C.POINTER(u32)]),
         "tlsgpu_group_open_host": (i32, [vp, vp, u32, vp, C.c_size_t, vp, C.c_size_t, vp]),
         "tlsgpu_group_seal_host": (i32, [vp, vp, u32, vp, C.c_size_t, vp, C.c_size_t, vp]),
@@ -414,6 +448,28 @@ class SessionTable:
         arr = (_SessionParams * len(params))(*[p.to_c() for p in params])
         _check(self.lib.tlsgpu_sessions_install(self.handle, first, len(params), arr),
                "tlsgpu_sessions_install")
+
+    def install_secrets(self, first: int, params: list[SecretParams]) -> None:
+        """TLS 1.3 sessions from their traffic secrets; the key schedule runs on
+        the device (tlsgpu_sessions_install_secrets)."""
+        arr = (_SecretParams * len(params))(*[p.to_c() for p in params])
+        _check(self.lib.tlsgpu_sessions_install_secrets(self.handle, first, len(params), arr),
+               "tlsgpu_sessions_install_secrets")
+
+    def key_update(self, ids_buf: int, n: int, status_buf: int, stream: int | None = None) -> None:
+        """KeyUpdate for the n slots whose ids (uint32, SESSION_NONE = skip) lie in
+        device memory at ids_buf; int32 statuses to status_buf.  Asynchronous
+        (tlsgpu_sessions_key_update)."""
+        _check(self.lib.tlsgpu_sessions_key_update(self.handle, ids_buf, n, status_buf, stream),
+               "tlsgpu_sessions_key_update")
+
+    def wire_key_update_ids(self, d_streams: int, d_results: int, n_streams: int, ids_buf: int,
+                            stream: int | None = None) -> None:
+        """The id list key_update takes, from an open_wire's results
+        (tlsgpu_wire_key_update_ids)."""
+        _check(self.lib.tlsgpu_wire_key_update_ids(self.handle, d_streams, d_results, n_streams,
+                                                   ids_buf, stream),
+               "tlsgpu_wire_key_update_ids")
 
     def hint(self, hints: int) -> None:
         """Batch-shape hints (tlsgpu_sessions_hint): HINT_NO_SHORT_RECORDS,
@@ -704,6 +760,11 @@ class GroupSessionTable:
         arr = (_SessionParams * len(params))(*[p.to_c() for p in params])
         _check(self.lib.tlsgpu_group_sessions_install(self.handle, first, len(params), arr),
                "tlsgpu_group_sessions_install")
+
+    def install_secrets(self, first: int, params: list[SecretParams]) -> None:
+        arr = (_SecretParams * len(params))(*[p.to_c() for p in params])
+        _check(self.lib.tlsgpu_group_sessions_install_secrets(self.handle, first, len(params), arr),
+               "tlsgpu_group_sessions_install_secrets")
 
     def open_host(self, h_recs: int, n: int, h_in: int, in_bytes: int, h_out: int,
                   out_bytes: int, h_status: int) -> None:

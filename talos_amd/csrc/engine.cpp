@@ -1,5 +1,6 @@
 // engine.cpp — the base of libtlsgpu.so's C ABI (include/tlsgpu.h): error
 // reporting, engines, session tables and their install (valid_params), the
+// device key schedule's calls (tlsgpu_sessions_install_secrets, _key_update), the
 // bitsliced AES-ECB self-test entry and the thin device helper API (memory,
 // streams, events).  The other host units: batch.cpp (the knobs, plan_batch /
 // run_batch, tlsgpu_open_batch / tlsgpu_seal_batch), host_paths.cpp
@@ -119,6 +120,8 @@ extern "C" void tlsgpu_sessions_destroy(tlsgpu_sessions* t) {
     }
   (void)hipFree(t->d_sess);
   (void)hipFree(t->d_gcm);
+  if (t->d_key_scratch) (void)hipFree(t->d_key_scratch);  // zero between calls
+  if (t->d_key_claim) (void)hipFree(t->d_key_claim);
   delete t;
 }
 
@@ -196,6 +199,157 @@ extern "C" int tlsgpu_sessions_install(tlsgpu_sessions* t, uint32_t first, uint3
       t->cc_padded = true;
     t->have[params[i].aead] = true;
   }
+  return TLSGPU_OK;
+}
+
+// ---------------------------------------------------------------------------
+// The device key schedule (include/tlsgpu.h; key_schedule.hip).
+// The launchers are weak references for the reason host_paths.cpp's are: a link
+// of the host objects against a launcher list written before these calls
+// existed (the CPU tests' recording HIP stub) must still resolve, and there the
+// calls fail loudly, after their argument checks and before any HIP call.
+namespace tg {
+__attribute__((weak)) int launch_tls13_derive(const tlsgpu_secret_params* secrets,
+                                              const DevSession* sessions, uint32_t capacity,
+                                              const uint32_t* ids, uint32_t first, uint32_t n,
+                                              uint32_t* claim, uint32_t epoch, KeyScratch* scratch,
+                                              int32_t* status, hipStream_t s);
+__attribute__((weak)) int launch_tls13_install(DevSession* sessions, DevGcmTables* tables,
+                                               const KeyScratch* scratch, uint32_t n,
+                                               hipStream_t s);
+__attribute__((weak)) int launch_wire_ku_ids(const tlsgpu_wire_stream* streams,
+                                             const tlsgpu_wire_result* results, uint32_t n_streams,
+                                             uint32_t* ids, hipStream_t s);
+}  // namespace tg
+
+static bool valid_secret(const tlsgpu_secret_params& p) {
+  uint32_t want = 0;
+  switch (p.aead) {
+    case TLSGPU_AES_128_GCM:
+    case TLSGPU_CHACHA20_POLY1305_TLS13: want = 32; break;  // SHA-256 suites
+    case TLSGPU_AES_256_GCM: want = 48; break;              // SHA-384
+    default: return false;
+  }
+  if (p.secret_len != want) return false;
+  // the padding block as valid_params has it
+  return p.pad_block <= 1 || (p.pad_block <= 16384 && (p.pad_block & (p.pad_block - 1)) == 0);
+}
+
+// derive + install + scrub of one chunk's scratch entries, queued on s
+static int queue_key_chunk(tlsgpu_sessions* t, const tlsgpu_secret_params* d_secrets,
+                           const uint32_t* d_ids, uint32_t first, uint32_t n, uint32_t epoch,
+                           int32_t* d_status, hipStream_t s) {
+  if (launch_tls13_derive(d_secrets, t->d_sess, t->capacity, d_ids, first, n, t->d_key_claim, epoch,
+                          t->d_key_scratch, d_status, s))
+    return -1;
+  if (!t->d_key_scratch) return 0;  // no slot of this table ever held a secret: statuses only
+  if (launch_tls13_install(t->d_sess, t->d_gcm, t->d_key_scratch, n, s)) return -1;
+  // the derived keys and secrets do not outlive the call in the scratch
+  return hipMemsetAsync(t->d_key_scratch, 0, sizeof(KeyScratch) * (size_t)n, s) == hipSuccess ? 0
+                                                                                               : -1;
+}
+
+extern "C" int tlsgpu_sessions_install_secrets(tlsgpu_sessions* t, uint32_t first, uint32_t n,
+                                               const tlsgpu_secret_params* params) {
+  if (!t || (!params && n)) return fail(TLSGPU_EINVAL, "bad arguments");
+  if ((uint64_t)first + n > t->capacity)
+    return fail(TLSGPU_ERANGE, "sessions [%u, %u) exceed capacity %u", first, first + n,
+                t->capacity);
+  for (uint32_t i = 0; i < n; i++)
+    if (!valid_secret(params[i])) return fail(TLSGPU_EINVAL, "invalid secret params at %u", i);
+  if (n == 0) return TLSGPU_OK;
+  {
+    // a TLS 1.3 install under the one-generation-per-table rule
+    std::lock_guard<std::mutex> lk(t->mu);
+    if (t->generation == 12)
+      return fail(TLSGPU_EINVAL, "TLS 1.3 traffic secrets in a TLS 1.2 session table");
+    if (!launch_tls13_derive || !launch_tls13_install)
+      return fail(TLSGPU_EHIP, "the key schedule kernels are not linked into this library");
+    t->generation = 13;
+  }
+  HIPCHK(hipSetDevice(t->eng->device));
+  hipStream_t s = t->eng->stream;
+  {
+    std::lock_guard<std::mutex> lk(t->mu);
+    if (!t->d_key_scratch) {
+      KeyScratch* sc = nullptr;
+      uint32_t* claim = nullptr;
+      if (hipMalloc(&sc, sizeof(KeyScratch) * (size_t)kKeyScratchEntries) != hipSuccess ||
+          hipMalloc(&claim, sizeof(uint32_t) * (size_t)t->capacity) != hipSuccess) {
+        (void)hipFree(sc);
+        return fail(TLSGPU_ENOMEM, "key schedule scratch");
+      }
+      hipError_t e1 = hipMemsetAsync(sc, 0, sizeof(KeyScratch) * (size_t)kKeyScratchEntries, s);
+      hipError_t e2 = hipMemsetAsync(claim, 0, sizeof(uint32_t) * (size_t)t->capacity, s);
+      if (e1 != hipSuccess || e2 != hipSuccess) {
+        (void)hipStreamSynchronize(s);
+        (void)hipFree(sc);
+        (void)hipFree(claim);
+        return fail(TLSGPU_EHIP, "key schedule scratch: %s",
+                    hipGetErrorString(e1 != hipSuccess ? e1 : e2));
+      }
+      t->d_key_claim = claim;
+      t->d_key_scratch = sc;
+    }
+  }
+  tlsgpu_secret_params* d_in = nullptr;
+  HIPCHK(hipMalloc(&d_in, sizeof(tlsgpu_secret_params) * (size_t)n));
+  hipError_t err = hipMemcpyAsync(d_in, params, sizeof(tlsgpu_secret_params) * (size_t)n,
+                                  hipMemcpyHostToDevice, s);
+  int rc = err == hipSuccess ? 0 : -1;
+  for (uint32_t off = 0; rc == 0 && off < n; off += kKeyScratchEntries)
+    rc = queue_key_chunk(t, d_in + off, nullptr, first + off, std::min(n - off, kKeyScratchEntries),
+                         0, nullptr, s);
+  // the secrets do not outlive the install in the staging copy
+  (void)hipMemsetAsync(d_in, 0, sizeof(tlsgpu_secret_params) * (size_t)n, s);
+  hipError_t serr = hipStreamSynchronize(s);
+  (void)hipFree(d_in);
+  if (err != hipSuccess || rc != 0 || serr != hipSuccess)
+    return fail(TLSGPU_EHIP, "secret install failed: %s",
+                hipGetErrorString(err != hipSuccess ? err : serr));
+  std::lock_guard<std::mutex> lk(t->mu);
+  for (uint32_t i = 0; i < n; i++) {
+    t->kinds[first + i] = params[i].aead;
+    t->tag_lens[first + i] = 16;
+    t->pad_masks[first + i] = (uint16_t)tls13_pad_mask(kTls13Version, params[i].pad_block);
+    if (params[i].aead == TLSGPU_CHACHA20_POLY1305_TLS13 && t->pad_masks[first + i])
+      t->cc_padded = true;
+    t->have[params[i].aead] = true;
+  }
+  return TLSGPU_OK;
+}
+
+extern "C" int tlsgpu_sessions_key_update(tlsgpu_sessions* t, const uint32_t* d_ids, uint32_t n,
+                                          int32_t* d_status, void* stream) {
+  if (!t || (n && (!d_ids || !d_status))) return fail(TLSGPU_EINVAL, "bad arguments");
+  if (n == 0) return TLSGPU_OK;
+  if (!launch_tls13_derive || !launch_tls13_install)
+    return fail(TLSGPU_EHIP, "the key schedule kernels are not linked into this library");
+  HIPCHK(hipSetDevice(t->eng->device));
+  hipStream_t s = stream ? (hipStream_t)stream : t->eng->stream;
+  // this call's claim value: unique among the table's calls and never 0, the
+  // value of a slot no call has claimed (a wrap after 2^32 calls skips it)
+  uint32_t epoch = t->key_epoch.fetch_add(1, std::memory_order_relaxed) + 1;
+  if (epoch == 0) epoch = t->key_epoch.fetch_add(1, std::memory_order_relaxed) + 1;
+  for (uint32_t off = 0; off < n; off += kKeyScratchEntries)
+    if (queue_key_chunk(t, nullptr, d_ids + off, 0, std::min(n - off, kKeyScratchEntries), epoch,
+                        d_status + off, s))
+      return fail(TLSGPU_EHIP, "key update: %s", hipGetErrorString(hipGetLastError()));
+  return TLSGPU_OK;
+}
+
+extern "C" int tlsgpu_wire_key_update_ids(tlsgpu_sessions* t, const tlsgpu_wire_stream* d_streams,
+                                          const tlsgpu_wire_result* d_results, uint32_t n_streams,
+                                          uint32_t* d_ids, void* stream) {
+  if (!t || (n_streams && (!d_streams || !d_results || !d_ids)))
+    return fail(TLSGPU_EINVAL, "bad arguments");
+  if (n_streams == 0) return TLSGPU_OK;
+  if (!launch_wire_ku_ids)
+    return fail(TLSGPU_EHIP, "the key schedule kernels are not linked into this library");
+  HIPCHK(hipSetDevice(t->eng->device));
+  if (launch_wire_ku_ids(d_streams, d_results, n_streams, d_ids,
+                         stream ? (hipStream_t)stream : t->eng->stream))
+    return fail(TLSGPU_EHIP, "key update ids: %s", hipGetErrorString(hipGetLastError()));
   return TLSGPU_OK;
 }
 

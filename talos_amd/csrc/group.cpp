@@ -194,6 +194,16 @@ extern "C" int tlsgpu_group_sessions_install(tlsgpu_group_sessions* gs, uint32_t
   });
 }
 
+extern "C" int tlsgpu_group_sessions_install_secrets(tlsgpu_group_sessions* gs, uint32_t first,
+                                                     uint32_t n,
+                                                     const tlsgpu_secret_params* params) {
+  if (!gs || (!params && n)) return gfail(TLSGPU_EINVAL, "group install: bad arguments");
+  std::lock_guard<std::mutex> lk(gs->g->mu);
+  return run_members(gs->g, [&](uint32_t k) {
+    return tlsgpu_sessions_install_secrets(gs->members[k], first, n, params);
+  });
+}
+
 extern "C" int tlsgpu_split_by_bytes(const tlsgpu_record* recs, uint32_t n, uint32_t parts,
                                      uint32_t* cuts) {
   if (!cuts || parts == 0 || (n && !recs)) return gfail(TLSGPU_EINVAL, "split_by_bytes: bad arguments");

@@ -76,6 +76,13 @@ struct tlsgpu_sessions {
   // EVP contexts: per-slot event of the slot's last install or scrub, so init
   // and cleanup need not wait on the device (created on a slot's first use)
   std::vector<hipEvent_t> slot_ev;
+  // The device key schedule (tlsgpu_sessions_install_secrets / _key_update):
+  // kKeyScratchEntries scratch entries and one claim word per slot, allocated by
+  // the first secret install (under mu) and never by a key update, which finds
+  // them there whenever a slot can hold a secret at all
+  tg::KeyScratch* d_key_scratch = nullptr;
+  uint32_t* d_key_claim = nullptr;
+  std::atomic<uint32_t> key_epoch{0};  // the last key update's claim value
   std::mutex mu;               // host mirrors, when several threads install at once
 };
 

@@ -1,5 +1,6 @@
 // tlsgpu_internal.h — layouts shared by the host units (the .cpp files) and the
-// HIP kernels (gcm_kernels.hip, chacha_kernels.hip, session_kernels.hip).
+// HIP kernels (gcm_kernels.hip, chacha_kernels.hip, session_kernels.hip,
+// key_schedule.hip).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -34,9 +35,17 @@ struct alignas(16) DevSession {
                               // xor3 + alignbit + xor3 column form
   uint32_t pad_mask;          // TLS 1.3 seal padding: block - 1 (a power of two), 0 = none;
                               // always 0 for a TLS 1.2 session (tls13_inner_len)
-  uint32_t reserved[111];
+  uint32_t secret_len;        // 0: the slot holds no traffic secret (every install from a key);
+                              // 32 / 48: secret[] is the TLS 1.3 traffic secret the slot's key
+                              // and IV come from, and the length is its hash (SHA-256 / SHA-384:
+                              // tlsgpu_sessions_install_secrets, tlsgpu_sessions_key_update)
+  uint8_t secret[48];
+  uint32_t reserved[98];
 };
 static_assert(sizeof(DevSession) == 1024, "DevSession layout");
+static_assert(offsetof(DevSession, pad_mask) == 576 && offsetof(DevSession, secret_len) == 580 &&
+                  offsetof(DevSession, secret) == 584 && offsetof(DevSession, reserved) == 632,
+              "DevSession layout");
 
 // "Is this session TLS 1.3?" (the RFC 8446 5.2-5.4 record layout): the ChaCha
 // kind that exists in TLS 1.3 only, or a GCM session without an explicit nonce.
@@ -457,6 +466,37 @@ int launch_fill_synthetic(uint8_t* d_out, uint64_t stride, uint32_t span_len,
 int launch_upload_session(const void* img, DevSession* sess, DevGcmTables* tab,
                           uint32_t table_bytes, hipStream_t s);
 int launch_scrub_session(DevSession* sess, DevGcmTables* tab, hipStream_t s);
+// The device key schedule (key_schedule.hip).  A table's
+// scratch holds one entry per session of a call's chunk: what the derive kernel
+// (one lane per entry) leaves for the install kernel (one wave per entry), and
+// what a hipMemsetAsync behind the two zeroes again.
+struct alignas(16) KeyScratch {
+  tlsgpu_session_params params;  // the derived key and IV as an install takes them
+  uint32_t secret_len;           // the secret the slot keeps: its length and bytes, laid
+  uint8_t secret[48];            // out as DevSession::secret_len / secret are
+  int32_t status;                // TLSGPU_OK: install it; anything else: skip the entry
+  uint32_t id;                   // the slot
+  uint32_t reserved;
+};
+static_assert(sizeof(KeyScratch) == 128 && sizeof(tlsgpu_session_params) == 64 &&
+                  sizeof(tlsgpu_secret_params) == 60,
+              "key schedule layouts");
+constexpr uint32_t kKeyScratchEntries = 65536;  // longer calls run in chunks of this
+// Derive n entries.  Install form (secrets != null): entry i is secrets[i] for
+// slot first + i.  Update form (secrets == null): entry i is slot ids[i] moved
+// to its next generation; `claim` (one word per slot) and `epoch` (unique per
+// call, never 0) let an id listed several times derive once: the first entry to
+// swap the epoch in owns the slot, the others report TLSGPU_OK and install
+// nothing.  status may be null (install form).  scratch == null (update form on
+// a table that never held a secret): statuses only.
+int launch_tls13_derive(const tlsgpu_secret_params* secrets, const DevSession* sessions,
+                        uint32_t capacity, const uint32_t* ids, uint32_t first, uint32_t n,
+                        uint32_t* claim, uint32_t epoch, KeyScratch* scratch, int32_t* status,
+                        hipStream_t s);
+int launch_tls13_install(DevSession* sessions, DevGcmTables* tables, const KeyScratch* scratch,
+                         uint32_t n, hipStream_t s);
+int launch_wire_ku_ids(const tlsgpu_wire_stream* streams, const tlsgpu_wire_result* results,
+                       uint32_t n_streams, uint32_t* ids, hipStream_t s);
 // GCM table bytes the default kernels read (basis + Shoup tables; the
 // bitsliced masks only in the experimental build)
 #ifdef TG_EXPERIMENTAL
