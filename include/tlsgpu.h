@@ -676,6 +676,85 @@ int tlsgpu_gather_wire(tlsgpu_sessions *t,
     tlsgpu_read_result *d_read_results, void *stream);
 
 /* ---------------------------------------------------------------------------
+ * One-call wire read path for TLS 1.2 tables: tlsgpu_open_wire and
+ * tlsgpu_gather_wire in one call that moves every application byte once.  Under
+ * TLS 1.2 a record's plaintext length (fragment - explicit nonce - tag) and its
+ * content type stand in its header, so each record's place in its stream's run
+ * at d_app + app_off is known before anything is opened, and the open writes it
+ * there, out of place.  The structs and the TLSGPU_READ_* codes are the ones
+ * above; `start` must be 0.  Asynchronous on `stream`.
+ *
+ * The rule, per stream (d_reads[i] / d_read_results[i] go with d_streams[i]):
+ * 1. Framing is tlsgpu_open_wire's: the same header checks, slot reservation,
+ *    max_records truncation and d_total, all-ones descriptors in unused slots.
+ * 2. The plan walks the framed records in order.  For record i: eiv = 8 for the
+ *    AES-GCM kinds, 0 for both ChaCha kinds; tag = the session's tag length
+ *    (truncated tags count); both 0 for an unknown session;
+ *    p_i = max(0, len_i - eiv - tag); T = the sum of p over the records placed so
+ *    far (64 bits); room = min(app_cap, app_bytes - app_off), 0 when app_off >
+ *    app_bytes.  Tested in this order:
+ *      start != 0: TLSGPU_READ_OUT_OF_BOUNDS, the stream is cut to nothing
+ *        (records = 0, consumed = 0);
+ *      the fragment [in_off, in_off + len_i) is not inside wire_bytes: the stream
+ *        is cut before record i with TLSGPU_READ_OUT_OF_BOUNDS, stop_type and
+ *        stop_len 0;
+ *      the header's type is not 23: cut before record i with
+ *        TLSGPU_READ_NOT_APP_DATA, stop_type = the header's type, stop_len = p_i;
+ *      T + p_i > room: cut before record i with TLSGPU_READ_FULL, stop_type 23,
+ *        stop_len = p_i;
+ *      otherwise the record is placed: its descriptor's out_off = app_off + T,
+ *        and T += p_i.  An empty record is placed and adds nothing; a fragment
+ *        shorter than eiv + tag has p_i = 0, is placed, fails the open with
+ *        TLSGPU_REC_PUBLIC_INVALID and ends the stream like any failure.  (With
+ *        app_off > app_bytes there is no room, so only empty records are placed:
+ *        their out_off is app_bytes, the buffer's end, not a byte outside it.)
+ *    stop_type and stop_len of a cut come from the record's UNVERIFIED header:
+ *    they say where the batch ends and nothing else, a forged type only shortens
+ *    it (as with the KeyUpdate peek above).  The type is part of the AAD, so
+ *    whoever opens the record next authenticates it.
+ *    A cut before record i is the KeyUpdate cut: the wire result's records,
+ *    delivered and alert_record become i, consumed ends with record i - 1's last
+ *    byte, a header-level alert that framing found behind the cut is dropped
+ *    (alert = 0; the next call finds it again), the descriptors from i on go
+ *    back to all ones (d_total still counts them; `first` stays what framing
+ *    reported, also for a stream cut to nothing), and not one byte of d_wire
+ *    from wire_off + consumed on is read by the open.
+ * 3. The open runs over d_recs from d_wire into d_app, bounded by wire_bytes and
+ *    app_bytes, with the cipher kernels of tlsgpu_open_batch.
+ * 4. The finish is tlsgpu_open_wire's: delivered, alert, alert_record,
+ *    TLSGPU_REC_SKIPPED, TLSGPU_REC_OVERFLOW.
+ * 5. The read result, with D = delivered: records = next = D; app_len = the sum
+ *    of the statuses of records 0 .. D - 1; consumed runs through record D - 1.
+ *    If D is below the stream's kept `records` (an AEAD failure or an over-long
+ *    plaintext ended it), stop = TLSGPU_READ_END and stop_type = stop_len = 0:
+ *    the wire result's alert says why, as ever.  Otherwise stop, stop_type and
+ *    stop_len are the plan's (TLSGPU_READ_END when it cut nothing).
+ *
+ * Memory.  d_wire is never written: a stream can be tried again.  A record that
+ * is not application data stays ciphertext at wire_off + consumed.  In d_app,
+ * bytes outside every stream's [app_off, app_off + room) are never written;
+ * [app_off, app_off + app_len) are the application bytes; from app_off + app_len
+ * up to app_off + T the bytes are unspecified (the failing record's zero-fill,
+ * the records behind it, an over-long record's plaintext); from app_off + T to
+ * the end of the room nothing is written.  To go on after a stop, build a stream
+ * at wire_off + consumed with seq + next and give it to tlsgpu_open_wire or to
+ * the caller's own record layer.
+ *
+ * TLSGPU_EINVAL before any GPU call: a null argument (tlsgpu_open_wire's and
+ * tlsgpu_gather_wire's rules together), d_app overlapping [d_wire, d_wire +
+ * wire_bytes), or a TLS 1.3 table (there the content length and the inner type
+ * exist only after the open: use tlsgpu_open_wire + tlsgpu_gather_wire).
+ * n_streams == 0 clears d_total and launches nothing more.  The KeyUpdate switch
+ * has no part in it (TLS 1.2), and the TaLoS read hook does not run here. */
+int tlsgpu_read_wire(tlsgpu_sessions *t,
+    const tlsgpu_wire_stream *d_streams, uint32_t n_streams,
+    const uint8_t *d_wire, size_t wire_bytes,
+    uint32_t max_records, tlsgpu_record *d_recs, int32_t *d_status,
+    tlsgpu_wire_result *d_results, uint32_t *d_total,
+    const tlsgpu_read_stream *d_reads, uint8_t *d_app, size_t app_bytes,
+    tlsgpu_read_result *d_read_results, void *stream);
+
+/* ---------------------------------------------------------------------------
  * Write-side framing: ssl3_write_bytes + do_ssl3_write
  * (ssl/s3_pkt.c:501-557, 560-762) for the AEAD suites, many connections at
  * once.  Each stream is one connection's SSL_write: data_len bytes of

@@ -202,6 +202,8 @@ def load_library(path: str = LIBPATH) -> C.CDLL:
         "tlsgpu_open_wire": (i32, [vp, vp, u32, vp, u32, vp, vp, vp, vp, vp]),
         "tlsgpu_gather_wire": (i32, [vp, vp, vp, u32, vp, vp, u32, vp, C.c_size_t, vp, vp,
                                      C.c_size_t, vp, vp]),
+        "tlsgpu_read_wire": (i32, [vp, vp, u32, vp, C.c_size_t, u32, vp, vp, vp, vp, vp, vp,
+                                   C.c_size_t, vp, vp]),
         "tlsgpu_open_host": (i32, [vp, vp, u32, vp, C.c_size_t, vp, C.c_size_t, vp]),
         "tlsgpu_seal_wire":(i32, [vp, vp, u32, vp, C.c_size_t, vp, C.c_size_t, u32, vp, vp, vp,
                                    vp, vp]),
@@ -593,6 +595,20 @@ def gather_wire(table: "SessionTable", d_streams: int, d_results: int, n_streams
     _check(table.lib.tlsgpu_gather_wire(table.handle, d_streams, d_results, n_streams, d_recs,
                                         d_status, max_records, d_wire, wire_bytes, d_reads, d_app,
                                         app_bytes, d_read_results, stream), "tlsgpu_gather_wire")
+
+
+def read_wire(table: "SessionTable", d_streams: int, n_streams: int, d_wire: int, wire_bytes: int,
+              max_records: int, d_recs: int, d_status: int, d_results: int, d_total: int,
+              d_reads: int, d_app: int, app_bytes: int, d_read_results: int,
+              stream: int | None = None) -> None:
+    """open_wire and gather_wire in one call for a TLS 1.2 table: each stream's records
+    are framed, cut before the first one that is not application data or does not
+    fit, and opened out of place straight into its contiguous run at d_app + app_off
+    (tlsgpu_read_wire).  d_wire is never written."""
+    _check(table.lib.tlsgpu_read_wire(table.handle, d_streams, n_streams, d_wire, wire_bytes,
+                                      max_records, d_recs, d_status, d_results, d_total, d_reads,
+                                      d_app, app_bytes, d_read_results, stream),
+           "tlsgpu_read_wire")
 
 
 def open_batch(table: SessionTable, d_recs: int, n: int, d_in: int, in_bytes: int, d_out: int,

@@ -1,7 +1,7 @@
 // host_paths.cpp — the batch ABI's paths around run_batch for data that starts
 // or ends on the host or on the wire: the host-resident pipeline
 // (tlsgpu_open_host / tlsgpu_seal_host), session owners and host delivery with
-// the TaLoS plaintext hooks, wire open, gather and seal, and the synthetic fills.
+// the TaLoS plaintext hooks, wire open, gather, read and seal, and the synthetic fills.
 #include "host_internal.h"
 
 using namespace tg;
@@ -444,6 +444,72 @@ extern "C" int tlsgpu_gather_wire(tlsgpu_sessions* t, const tlsgpu_wire_stream* 
   if (launch_wire_gather_copy(d_recs, d_status, max_records, d_wire, wire_bytes, dst, d_app,
                               app_bytes, gather_piece(wire_bytes, max_records), s))
     return fail(TLSGPU_EHIP, "wire gather copy launch: %s", hipGetErrorString(hipGetLastError()));
+  return TLSGPU_OK;
+}
+
+// tlsgpu_read_wire (include/tlsgpu.h "One-call wire read path"; DESIGN.md
+// §4.6e): tlsgpu_open_wire's framing, a plan that gives every record its place in
+// its stream's application run, the open out of place from d_wire into d_app, and
+// the two finishes.  The destinations travel in the descriptors: no scratch of
+// this call's own lives across run_batch.  The plan's and the read finish's
+// launchers are weak references for the reason the gather's are (above).
+namespace tg {
+__attribute__((weak)) int launch_wire_read_plan(
+    const tlsgpu_wire_stream* streams, uint32_t n_streams, const DevSession* sessions,
+    uint32_t n_sessions, uint32_t max_records, uint64_t wire_bytes,
+    const tlsgpu_read_stream* reads, uint64_t app_bytes, tlsgpu_record* recs,
+    tlsgpu_wire_result* results, tlsgpu_read_result* out, hipStream_t s);
+__attribute__((weak)) int launch_wire_read_finish(
+    const tlsgpu_wire_stream* streams, const tlsgpu_wire_result* results, uint32_t n_streams,
+    const tlsgpu_record* recs, const int32_t* status, uint32_t max_records,
+    tlsgpu_read_result* out, hipStream_t s);
+}  // namespace tg
+
+extern "C" int tlsgpu_read_wire(tlsgpu_sessions* t, const tlsgpu_wire_stream* d_streams,
+                                uint32_t n_streams, const uint8_t* d_wire, size_t wire_bytes,
+                                uint32_t max_records, tlsgpu_record* d_recs, int32_t* d_status,
+                                tlsgpu_wire_result* d_results, uint32_t* d_total,
+                                const tlsgpu_read_stream* d_reads, uint8_t* d_app,
+                                size_t app_bytes, tlsgpu_read_result* d_read_results,
+                                void* stream) {
+  if (!t || !d_total ||
+      (n_streams && (!d_streams || !d_wire || !d_results || !d_reads || !d_app ||
+                     !d_read_results)) ||
+      (max_records && (!d_recs || !d_status)))
+    return fail(TLSGPU_EINVAL, "bad arguments");
+  // the open reads d_wire while it writes d_app: the two may not share a byte
+  const uintptr_t w0 = (uintptr_t)d_wire, a0 = (uintptr_t)d_app;
+  if (d_wire && d_app && a0 < w0 + wire_bytes && w0 < a0 + app_bytes)
+    return fail(TLSGPU_EINVAL, "d_app overlaps d_wire");
+  // a TLS 1.3 record's content length and inner type exist only after the open
+  if (t->generation == 13)
+    return fail(TLSGPU_EINVAL, "tlsgpu_read_wire takes TLS 1.2 session tables: read TLS 1.3 "
+                               "streams with tlsgpu_open_wire + tlsgpu_gather_wire");
+  if (!launch_wire_read_plan || !launch_wire_read_finish)
+    return fail(TLSGPU_EHIP, "the read kernels are not linked into this library");
+  HIPCHK(hipSetDevice(t->eng->device));
+  hipStream_t s = stream ? (hipStream_t)stream : t->eng->stream;
+  HIPCHK(hipMemsetAsync(d_total, 0, sizeof(uint32_t), s));
+  if (n_streams == 0) return TLSGPU_OK;
+  // unused record slots name no session (0xFFFFFFFF): the open kernels skip them
+  if (max_records) HIPCHK(hipMemsetAsync(d_recs, 0xFF, sizeof(tlsgpu_record) * (size_t)max_records, s));
+  if (launch_wire_frame(d_streams, n_streams, d_wire, t->d_sess, t->capacity, max_records, d_recs,
+                        d_results, d_total, s))
+    return fail(TLSGPU_EHIP, "wire frame launch: %s", hipGetErrorString(hipGetLastError()));
+  // before anything is opened: where each record's plaintext goes, and where each stream ends
+  if (launch_wire_read_plan(d_streams, n_streams, t->d_sess, t->capacity, max_records, wire_bytes,
+                            d_reads, app_bytes, d_recs, d_results, d_read_results, s))
+    return fail(TLSGPU_EHIP, "wire read plan launch: %s", hipGetErrorString(hipGetLastError()));
+  if (max_records) {
+    const Bounds b = {wire_bytes, app_bytes};
+    int rc = run_batch(t, d_recs, max_records, d_wire, d_app, d_status, s, false, false, &b);
+    if (rc != TLSGPU_OK) return rc;
+  }
+  if (launch_wire_finish(n_streams, d_results, d_status, s))
+    return fail(TLSGPU_EHIP, "wire finish launch: %s", hipGetErrorString(hipGetLastError()));
+  if (launch_wire_read_finish(d_streams, d_results, n_streams, d_recs, d_status, max_records,
+                              d_read_results, s))
+    return fail(TLSGPU_EHIP, "wire read finish launch: %s", hipGetErrorString(hipGetLastError()));
   return TLSGPU_OK;
 }
 

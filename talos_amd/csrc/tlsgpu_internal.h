@@ -461,6 +461,20 @@ int launch_wire_peek13(const tlsgpu_wire_stream* streams, uint32_t n_streams, co
 int launch_wire_ku_confirm(const tlsgpu_wire_stream* streams, uint32_t n_streams,
                            const uint8_t* wire, uint32_t max_records, const tlsgpu_record* recs,
                            const int32_t* status, tlsgpu_wire_result* results, hipStream_t s);
+// tlsgpu_read_wire (wire_read.hip).  The plan runs between launch_wire_frame and
+// an out-of-place open into d_app: it gives every placed record its destination
+// (out_off), cuts each stream before the first record that is not placed
+// (descriptors from there on back to all ones, the wire result rewritten) and
+// leaves the stop in `out`.  The finish runs after launch_wire_finish and
+// completes `out` from the delivered records' statuses.
+int launch_wire_read_plan(const tlsgpu_wire_stream* streams, uint32_t n_streams,
+                          const DevSession* sessions, uint32_t n_sessions, uint32_t max_records,
+                          uint64_t wire_bytes, const tlsgpu_read_stream* reads, uint64_t app_bytes,
+                          tlsgpu_record* recs, tlsgpu_wire_result* results, tlsgpu_read_result* out,
+                          hipStream_t s);
+int launch_wire_read_finish(const tlsgpu_wire_stream* streams, const tlsgpu_wire_result* results,
+                            uint32_t n_streams, const tlsgpu_record* recs, const int32_t* status,
+                            uint32_t max_records, tlsgpu_read_result* out, hipStream_t s);
 int launch_fill_synthetic(uint8_t* d_out, uint64_t stride, uint32_t span_len,
                           uint32_t n, uint64_t seed, uint64_t index0, hipStream_t s);
 int launch_upload_session(const void* img, DevSession* sess, DevGcmTables* tab,
