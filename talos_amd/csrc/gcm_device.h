@@ -1070,6 +1070,27 @@ __device__ __forceinline__ void aes_roundN(uint32_t (&s)[NB][4], uint32_t k0, ui
 #endif
 }
 
+// Rounds 3 .. ROUNDS of NB blocks whose state after round 2 is in A (the
+// round-2 cache below).  aes_ctr16xN keeps these rounds in its own body:
+// calling this tail from it gave the queue kernel's pack variants another
+// schedule (4 -> 14 VGPR spills), and their code is to stay as it is.
+template <int NB, int ROUNDS, class Hook>
+__device__ __forceinline__ void aes_ctr16xN_tail(uint32_t (&ks)[NB][4], uint32_t (&A)[NB][4],
+                                                 cu32* rk, cu32* rkr, uint32_t laneoff,
+                                                 Hook&& hook) {
+#pragma unroll
+  for (int r = 3; r < ROUNDS; r++) {
+    aes_roundN<NB>(A, rkr[4 * r], rkr[4 * r + 1], rkr[4 * r + 2], rkr[4 * r + 3], laneoff);
+    hook(r);  // work independent of A (GHASH of the previous group) between rounds
+  }
+#pragma unroll
+  for (int b = 0; b < NB; b++) {
+    aes_last(A[b][0], A[b][1], A[b][2], A[b][3], rk + 4 * ROUNDS, laneoff);
+#pragma unroll
+    for (int w = 0; w < 4; w++) ks[b][w] = A[b][w];
+  }
+}
+
 // NB keystream blocks for counters ctr[b] < 2^16 (aes_ctr16 generalised).
 template <int NB, int ROUNDS, class Hook>
 __device__ __forceinline__ void aes_ctr16xN(uint32_t (&ks)[NB][4], const uint32_t (&ctr)[NB],
@@ -1097,6 +1118,48 @@ __device__ __forceinline__ void aes_ctr16xN(uint32_t (&ks)[NB][4], const uint32_
     for (int w = 0; w < 4; w++) ks[b][w] = A[b][w];
   }
 }
+
+// ---------------------------------------------------------------------------
+// Round-2 cache (the queue kernel's open no-pack variants of the TLS 1.2
+// unit).
+// For a counter below 2^16 the state after round 2 separates exactly,
+//   state2(ctr) = F(ctr & 0xFF) ^ G(ctr >> 8) ^ k2,
+// F the four T-table words fed by s0 = k1a ^ rotl16(TE1(v, 3)) and G the four
+// fed by s1 = k1b ^ rotl16(TE0(v, 2)) in aes_ctr16xN above.  A record's block
+// i runs in lane i % 64 at step i / 64 with counter 2 + i (J0 = IV || 1), so a
+// lane's low counter byte at step s is that of step s & 3: four F variants per
+// lane and record, k2 folded in, 20 lookups instead of 5 per block.  The high
+// byte is s >> 2 in lanes 0..61 and (s + 1) >> 2 in lanes 62 and 63, which
+// carry one step early — it is not wave-uniform.  G is looked up once per four
+// steps, at s % 4 == 0, for the high byte of step s + 3: the value of all four
+// steps in lanes 0..61 and of step s + 3 only in lanes 62 and 63, which take
+// lanes 58..61's words (r2c_before_carry) for the three steps before.
+__device__ __forceinline__ void r2c_build_f(uint32_t (&F)[4][4], uint32_t ctr_lane,
+                                            const RecConsts& c, uint32_t rk03, uint32_t laneoff) {
+#pragma unroll
+  for (int v = 0; v < 4; v++) {
+    const uint32_t x = bswap32(ctr_lane + kWave * v) ^ rk03;
+    const uint32_t s0 = c.k1a ^ rotl16(TE1(x, 3));
+    F[v][0] = c.k2[0] ^ TE0(s0, 0);
+    F[v][1] = c.k2[1] ^ rotl16(TE1(s0, 3));
+    F[v][2] = c.k2[2] ^ rotl16(TE0(s0, 2));
+    F[v][3] = c.k2[3] ^ TE1(s0, 1);
+  }
+}
+__device__ __forceinline__ void r2c_lookup_g(uint32_t (&G)[4], uint32_t ctr, const RecConsts& c,
+                                             uint32_t rk03, uint32_t laneoff) {
+  const uint32_t x = bswap32(ctr) ^ rk03;
+  const uint32_t s1 = c.k1b ^ rotl16(TE0(x, 2));
+  G[0] = TE1(s1, 1);
+  G[1] = TE0(s1, 0);
+  G[2] = rotl16(TE1(s1, 3));
+  G[3] = rotl16(TE0(s1, 2));
+}
+// G of the steps before lanes 62 and 63 carry: lanes 60..63 take the word of
+// the lane two below (row_shr:2 on row 3, bank 3), every other lane its own.
+__device__ __forceinline__ uint32_t r2c_before_carry(uint32_t g) {
+  return (uint32_t)__builtin_amdgcn_update_dpp((int)g, (int)g, 0x112, 0x8, 0x8, false);
+}
 template <int NB, int ROUNDS>
 __device__ __forceinline__ void aes_ctr16xN(uint32_t (&ks)[NB][4], const uint32_t (&ctr)[NB],
                                             const RecConsts& c, uint32_t rk03, cu32* rk,
@@ -1120,9 +1183,14 @@ __device__ __forceinline__ void aes_ctr16xN(uint32_t (&ks)[NB][4], const uint32_
 //     step follows the loop.  A record's first group (its ciphertext loads
 //     were issued just before) takes step b after round FR0 + FRS * b, so a
 //     caller can put the wave's wait for those loads some rounds later.
+// R2C: rounds 1 and 2 from the per-lane round-2 cache above instead of ten
+// lookups per block (NB = 2 and start = 0 only; the F variants are built behind
+// the first group's loads, G at every fourth step, so nothing of an earlier
+// record is seen).
 // Advances `start` past the groups done; the caller finishes the record with
 // gcm_blocks.
-template <bool SEAL, int ROUNDS, int NB, class G, bool OWN = false, int FR0 = 3, int FRS = 2>
+template <bool SEAL, int ROUNDS, int NB, class G, bool OWN = false, int FR0 = 3, int FRS = 2,
+          bool R2C = false>
 __device__ __forceinline__ void gcm_blocks_xN(const RecCtx& rc, const DevSession* __restrict__ S,
                                               const RecConsts& rcc, uint32_t (&x)[4],
                                               uint32_t& start, uint32_t lane, uint32_t laneoff,
@@ -1163,6 +1231,12 @@ __device__ __forceinline__ void gcm_blocks_xN(const RecCtx& rc, const DevSession
     for (int b = 0; b < NB; b++)
       if (r == FR0 + FRS * b) ghash_step(b);
   };
+  [[maybe_unused]] uint32_t F2[4][4], G2[4];  // the round-2 cache (R2C)
+  if constexpr (R2C) {
+    static_assert(NB == 2, "the round-2 cache's step map is that of two blocks per lane");
+    if (start != 0) return;  // t even and a G lookup in the first trip (the caller's tail is right)
+    r2c_build_f(F2, ctr0 + lane, rcc, rk03, laneoff);
+  }
   lap_if(hc, kLapFirst, lane);  // the first group's loads are issued, not waited for
   bool first = true;
   for (; t + NB <= nfull_steps; t += NB, start += NB * kWave) {
@@ -1175,8 +1249,39 @@ __device__ __forceinline__ void gcm_blocks_xN(const RecCtx& rc, const DevSession
     uint32_t ctr[NB], k[NB][4];
 #pragma unroll
     for (int b = 0; b < NB; b++) ctr[b] = ctr0 + i + kWave * b;
-    // a record's first group: no hook (nothing to hash yet), or its own rounds
-    if (first) {
+    [[maybe_unused]] uint32_t A[NB][4];
+    if constexpr (R2C) {
+      // steps t (even) and t + 1: variants t & 3 and (t & 3) + 1, G of the
+      // steps before the carry except at t + 1 = 3 mod 4
+      // a wave-uniform branch on t & 2, so every F2 index is static: four
+      // XORs per block, and the G lookup sits in the branch it belongs to
+      // (one body with a masked select of the variants measured slower than
+      // the ten lookups: profiles/r09_round2_cache.txt)
+      if ((t & 2u) == 0) {
+        r2c_lookup_g(G2, ctr0 + lane + kWave * (t + 3u), rcc, rk03, laneoff);
+#pragma unroll
+        for (int w = 0; w < 4; w++) {
+          const uint32_t gb = r2c_before_carry(G2[w]);
+          A[0][w] = F2[0][w] ^ gb;
+          A[1][w] = F2[1][w] ^ gb;
+        }
+      } else {
+#pragma unroll
+        for (int w = 0; w < 4; w++) {
+          A[0][w] = F2[2][w] ^ r2c_before_carry(G2[w]);
+          A[1][w] = F2[3][w] ^ G2[w];
+        }
+      }
+      if (first) {
+        if constexpr (kLateGh)
+          aes_ctr16xN_tail<NB, ROUNDS>(k, A, rk, rkr, laneoff, [](int) {});
+        else
+          aes_ctr16xN_tail<NB, ROUNDS>(k, A, rk, rkr, laneoff, hook_first);
+      } else {
+        aes_ctr16xN_tail<NB, ROUNDS>(k, A, rk, rkr, laneoff, hook);
+      }
+    } else if (first) {
+      // a record's first group: no hook (nothing to hash yet), or its own rounds
       if constexpr (kLateGh)
         aes_ctr16xN<NB, ROUNDS>(k, ctr, rcc, rk03, rk, rkr, laneoff);
       else
@@ -1209,7 +1314,7 @@ __device__ __forceinline__ void gcm_blocks_xN(const RecCtx& rc, const DevSession
 // OWN: open hashes each group in its own AES rounds, a record's first group
 // one round apart with the last step after round ROUNDS - 2 (the queue
 // kernel's no-pack variants).
-template <bool SEAL, int ROUNDS, int NB = 4, class G = GhLane, bool OWN = false>
+template <bool SEAL, int ROUNDS, int NB = 4, class G = GhLane, bool OWN = false, bool R2C = false>
 __device__ void gcm_record_x4(const RecCtx& rc, const DevSession* __restrict__ S,
                               const RecConsts& rcc, int32_t* status_slot, uint32_t lane,
                               uint32_t laneoff, const G& gl,
@@ -1221,7 +1326,7 @@ __device__ void gcm_record_x4(const RecCtx& rc, const DevSession* __restrict__ S
     x[2] = bswap32(rc.aad_be[2]); x[3] = bswap32(rc.aad_be[3]);
   }
   uint32_t start = 0;
-  gcm_blocks_xN<SEAL, ROUNDS, NB, G, OWN, OWN ? ROUNDS - 1 - NB : 3, OWN ? 1 : 2>(
+  gcm_blocks_xN<SEAL, ROUNDS, NB, G, OWN, OWN ? ROUNDS - 1 - NB : 3, OWN ? 1 : 2, R2C>(
       rc, S, rcc, x, start, lane, laneoff, gl, hc);
 #ifdef TG_XN_ODD_STEP
   // an odd full step left by the NB-wide loop: the pipelined one-step loop

@@ -340,7 +340,7 @@ __device__ __forceinline__ RecConsts rec_consts_fresh(const RecPre* p) {
 
 // G: GhLaneLen from the queue kernel (it builds the run's lengths-block table),
 // GhLane from kernels that do not (experimental/gcm_fused.h).
-template <bool SEAL, int ROUNDS, int NB = 4, class G = GhLane, bool OWN = false>
+template <bool SEAL, int ROUNDS, int NB = 4, class G = GhLane, bool OWN = false, bool R2C = false>
 __device__ __forceinline__ void hy_tt_record(const BatchArgs& a, const RecPre* __restrict__ pre,
                                              uint32_t r, const DevSession* __restrict__ S,
                                              uint32_t lane, uint32_t laneoff, const G& gl,
@@ -367,7 +367,8 @@ __device__ __forceinline__ void hy_tt_record(const BatchArgs& a, const RecPre* _
     asm volatile("" ::"s"(rcc.k2[3]));
     hc->lap(kLapConsts, lane);
   }
-  gcm_record_x4<SEAL, ROUNDS, NB, G, OWN>(rc, S, rcc, a.status + r, lane, laneoff, gl, a.dbg, hc);
+  gcm_record_x4<SEAL, ROUNDS, NB, G, OWN, R2C>(rc, S, rcc, a.status + r, lane, laneoff, gl, a.dbg,
+                                               hc);
 }
 
 // Packed bitsliced wave role: a record of a_min..16384
@@ -856,6 +857,16 @@ __global__ __launch_bounds__(NT, 1) void TG_GEN(gcm_hy_kernel)(BatchArgs a,
   // the order and the tables code they had.
   constexpr bool kOwnRounds = !PACK;
   constexpr bool kOpaqueTables = !PACK;
+  // open no-pack only: AES rounds 1 and 2 from the per-lane round-2 cache
+  // (gcm_device.h; B +1.75 % same-box).  Seal compiles with it
+  // too but no benchmark config measures seal, so it keeps its code, and the
+  // TLS 1.3 unit's open kernel spills 12 VGPRs to scratch with it (0 without).
+  // TG_NO_R2_CACHE: the ten lookups per block, for A/B builds
+#ifndef TG_NO_R2_CACHE
+  constexpr bool kRound2Cache = !PACK && !SEAL && NB == 2 && !kTls13;
+#else
+  constexpr bool kRound2Cache = false;
+#endif
   const uint32_t lane = threadIdx.x & 63;
   const uint32_t wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   const uint32_t laneoff = aes_laneoff(lane);
@@ -1148,8 +1159,8 @@ __global__ __launch_bounds__(NT, 1) void TG_GEN(gcm_hy_kernel)(BatchArgs a,
             else __builtin_amdgcn_s_setprio(1);
           }
 #endif
-          hy_tt_record<SEAL, ROUNDS, NB, GhLaneLen, kOwnRounds>(a, pre, r, S, lane, laneoff, gl,
-                                                               kHandoverLaps ? &hc : nullptr);
+          hy_tt_record<SEAL, ROUNDS, NB, GhLaneLen, kOwnRounds, kRound2Cache>(
+              a, pre, r, S, lane, laneoff, gl, kHandoverLaps ? &hc : nullptr);
 #ifndef TG_NO_TAIL_PRIO
           if (!BSW && !PACK) __builtin_amdgcn_s_setprio(0);
 #endif
