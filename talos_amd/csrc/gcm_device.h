@@ -337,8 +337,14 @@ struct GhLane {
 // the queue kernel's policy.  gcm_finish then takes LEN * H from the table
 // instead of folding the lengths block into a lane chain (gcm_close_len).
 struct GhLaneLen : GhLane {};
+// GhLaneLen whose chain weights take one reduction per multiply
+// (mul_shoup_fold): the queue kernel's no-pack variants.
+struct GhLaneFold : GhLane {
+  __device__ __forceinline__ void shoup(const uint32_t X[4], uint32_t e, uint32_t Z[4]) const;
+};
 template <class G> inline constexpr bool gh_has_len_table = false;
 template <> inline constexpr bool gh_has_len_table<GhLaneLen> = true;
+template <> inline constexpr bool gh_has_len_table<GhLaneFold> = true;
 
 __device__ __forceinline__ GhLane gh_lane(uint32_t lane) {
   GhLane g;
@@ -514,11 +520,81 @@ __device__ __forceinline__ void mul_shoup_ahead(const uint32_t X[4], uint32_t e,
   Z[0] = z0; Z[1] = z1; Z[2] = z2; Z[3] = z3;
 }
 
+// One reduction for a whole multiply.  s(Z) = (Z >> 4) ^ rem4(Z & 0xF) is the
+// multiplication by x^4 modulo the GCM polynomial and linear, so the Horner
+// sum of mul_shoup, sum_k s^(31-k)(T[nib_k]), may be added up unreduced as the
+// 256-bit value W = sum_k (T[nib_k] << 128) >> 4 (31 - k) (BE words, W[0] the
+// high one; its low four bits are zero) and reduced once: bit 127 - j of
+// O = W[4..7] stands for x^(128 + j) = x^j (1 + x + x^2 + x^7), so
+// Z = W[0..3] ^ O ^ (O >> 1) ^ (O >> 2) ^ (O >> 7).  Of the bits the shifts
+// drop only bits 6..4 of O can be set (in O >> 7: x^(128 + j'), j' = 0..2);
+// they are folded the same way once more, within the high word.
+__device__ __forceinline__ void gh_fold(const uint32_t W[8], uint32_t Z[4]) {
+  const uint32_t* O = W + 4;
+  const uint32_t t = O[3] << 25;
+  Z[0] = xor3(W[0], O[0], O[0] >> 1) ^ xor3(O[0] >> 2, O[0] >> 7, xor3(t, t >> 1, t >> 2)) ^ (t >> 7);
+#pragma unroll
+  for (int w = 1; w < 4; w++)
+    Z[w] = xor3(W[w], O[w], __builtin_amdgcn_alignbit(O[w - 1], O[w], 1)) ^
+           __builtin_amdgcn_alignbit(O[w - 1], O[w], 2) ^ __builtin_amdgcn_alignbit(O[w - 1], O[w], 7);
+}
+
+// z = x * H^e as mul_shoup gives it (the same 32 table reads), with gh_fold's
+// single reduction instead of a 31-step dependent chain.  The four nibbles at
+// bit 4 j of X[0..3] share the bit shift 4 (7 - j), and their entries lie whole
+// words apart (X[c]'s c words down): group j XORs its four entries into a
+// seven-word sum by word placement, shifts that once across the words and adds
+// it to W.  The next group's reads are issued before a group is combined (8
+// reads, 32 VGPRs, in flight at the most); shifts and nibble positions are
+// inline constants.  The queue kernels' record finish (GhLaneFold).
+__device__ __forceinline__ void mul_shoup_fold(const uint32_t X[4], uint32_t e, uint32_t Z[4]) {
+  const uint32_t base = sh_base(e);
+  uint32_t W[8];
+  uint4 tt[2][4];
+#pragma unroll
+  for (int c = 0; c < 4; c++) tt[1][c] = lds_u128(base + ((X[c] >> 28) & 0xF) * 256);
+#pragma unroll
+  for (int j = 7; j >= 0; j--) {
+    const uint4* t = tt[j & 1];
+    if (j > 0) {
+#pragma unroll
+      for (int c = 0; c < 4; c++) tt[(j - 1) & 1][c] = lds_u128(base + ((X[c] >> (4 * (j - 1))) & 0xF) * 256);
+    }
+    uint32_t S[7];
+    S[0] = t[0].x;
+    S[1] = t[0].y ^ t[1].x;
+    S[2] = xor3(t[0].z, t[1].y, t[2].x);
+    S[3] = xor3(t[0].w, t[1].z, t[2].y) ^ t[3].x;
+    S[4] = xor3(t[1].w, t[2].z, t[3].y);
+    S[5] = t[2].w ^ t[3].z;
+    S[6] = t[3].w;
+    if (j == 7) {  // no shift; W's low word is still empty
+#pragma unroll
+      for (int w = 0; w < 7; w++) W[w] = S[w];
+      W[7] = 0;
+    } else {
+      const int sh = 4 * (7 - j);
+      W[0] ^= S[0] >> sh;
+#pragma unroll
+      for (int w = 1; w < 7; w++) W[w] ^= __builtin_amdgcn_alignbit(S[w - 1], S[w], sh);
+      W[7] ^= S[6] << (32 - sh);
+    }
+    // W group by group: left to itself the compiler sums word by word over
+    // all eight groups, with all 32 reads (128 VGPRs) in flight
+    asm volatile("" : "+v"(W[0]), "+v"(W[1]), "+v"(W[2]), "+v"(W[3]), "+v"(W[4]), "+v"(W[5]),
+                      "+v"(W[6]), "+v"(W[7]));
+  }
+  gh_fold(W, Z);
+}
+
 __device__ __forceinline__ void GhLane::mul64(const uint32_t x[4], uint32_t o[4]) const {
   mul_k(x, o, *this);
 }
 __device__ __forceinline__ void GhLane::shoup(const uint32_t X[4], uint32_t e, uint32_t Z[4]) const {
   mul_shoup_ahead(X, e, Z);
+}
+__device__ __forceinline__ void GhLaneFold::shoup(const uint32_t X[4], uint32_t e, uint32_t Z[4]) const {
+  mul_shoup_fold(X, e, Z);
 }
 
 // Two independent Shoup multiplies, interleaved; e == 0 gives zero.
@@ -1630,23 +1706,32 @@ __device__ void load_len_table(const DevGcmTables* __restrict__ tab) {
   if (i >= kLenEntries) return;
   const uint32_t p = i >> 4;
   const bool aad = p == kLenRows;
-  const uint32_t k = aad ? 17u : p;
-  uint4 z = sh[aad ? ab >> 4 : i & 15u];
-  auto shift = [](uint4& v) {
-    const uint32_t rem = v.w & 0xF;
-    v.w = __builtin_amdgcn_alignbit(v.z, v.w, 4);
-    v.z = __builtin_amdgcn_alignbit(v.y, v.z, 4);
-    v.y = __builtin_amdgcn_alignbit(v.x, v.y, 4);
-    v.x = (v.x >> 4) ^ rem4(rem);
-  };
+  // s^(31 - k) as one shift by 4 (31 - k) bits and one gh_fold: nibble p < 6
+  // moves down three words and 28 - 4 p bits, the AAD's nibbles 17 and 16 one
+  // word and 24 and 28 bits
+  const uint4 z = sh[aad ? ab >> 4 : i & 15u];
+  const uint32_t r = aad ? 24u : 28u - 4u * p;
+  uint32_t v[5];  // (z << 32) >> r
+  v[0] = z.x >> r;
+  v[1] = __builtin_amdgcn_alignbit(z.x, z.y, r);
+  v[2] = __builtin_amdgcn_alignbit(z.y, z.z, r);
+  v[3] = __builtin_amdgcn_alignbit(z.z, z.w, r);
+  v[4] = __builtin_amdgcn_alignbit(z.w, 0u, r);  // (row 7: r = 0, zeroed below)
   if (aad) {
-    uint4 u = sh[ab & 15u];
-    shift(u);
-    z.x ^= u.x; z.y ^= u.y; z.z ^= u.z; z.w ^= u.w;
+    const uint4 u = sh[ab & 15u];
+    v[0] ^= u.x >> 28;
+    v[1] ^= __builtin_amdgcn_alignbit(u.x, u.y, 28);
+    v[2] ^= __builtin_amdgcn_alignbit(u.y, u.z, 28);
+    v[3] ^= __builtin_amdgcn_alignbit(u.z, u.w, 28);
+    v[4] ^= u.w << 4;
   }
-  for (uint32_t s = k; s < 31; s++) shift(z);
-  if (p > kLenRows) z = make_uint4(0, 0, 0, 0);
-  *reinterpret_cast<uint4*>(s_lds + LEN_OFF + 16u * i) = z;
+  const uint32_t W[8] = {0u, aad ? v[0] : 0u, aad ? v[1] : 0u, aad ? v[2] : v[0],
+                         aad ? v[3] : v[1], aad ? v[4] : v[2], aad ? 0u : v[3], aad ? 0u : v[4]};
+  uint32_t f[4];
+  gh_fold(W, f);
+  uint4 o = make_uint4(f[0], f[1], f[2], f[3]);
+  if (p > kLenRows) o = make_uint4(0, 0, 0, 0);
+  *reinterpret_cast<uint4*>(s_lds + LEN_OFF + 16u * i) = o;
 }
 
 // Bitsliced round-key masks from the round-key words (SGPRs): s_bfe_i32

@@ -7,6 +7,7 @@
 // Instantiated per variant in gcm_queue.hip / gcm_hy128.hip / gcm_hy256.hip so
 // that the (slow to compile) bitsliced instantiations build in parallel.
 #pragma once
+#include <type_traits>
 #include <utility>
 
 #include "gcm_device.h"
@@ -870,7 +871,10 @@ __global__ __launch_bounds__(NT, 1) void TG_GEN(gcm_hy_kernel)(BatchArgs a,
   const uint32_t lane = threadIdx.x & 63;
   const uint32_t wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   const uint32_t laneoff = aes_laneoff(lane);
-  const GhLaneLen gl{gh_lane(lane)};  // + the run's lengths-block table
+  // + the run's lengths-block table; the no-pack variants' record finish takes
+  // one reduction per multiply (the pack variants keep their code, as above)
+  using GL = std::conditional_t<PACK, GhLaneLen, GhLaneFold>;
+  const GL gl{gh_lane(lane)};
   const tlsgpu_record* D = reinterpret_cast<const tlsgpu_record*>(a.descs);
   const bool bs_role = wave < (uint32_t)BSW;
   if (BSW && !bs_role) __builtin_amdgcn_s_setprio(1);
@@ -1159,7 +1163,7 @@ __global__ __launch_bounds__(NT, 1) void TG_GEN(gcm_hy_kernel)(BatchArgs a,
             else __builtin_amdgcn_s_setprio(1);
           }
 #endif
-          hy_tt_record<SEAL, ROUNDS, NB, GhLaneLen, kOwnRounds, kRound2Cache>(
+          hy_tt_record<SEAL, ROUNDS, NB, GL, kOwnRounds, kRound2Cache>(
               a, pre, r, S, lane, laneoff, gl, kHandoverLaps ? &hc : nullptr);
 #ifndef TG_NO_TAIL_PRIO
           if (!BSW && !PACK) __builtin_amdgcn_s_setprio(0);
